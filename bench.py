@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: residues/s of the packed ESM-2 forward on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model esm2_650m] [--tokens 50000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model esm2_650m] [--tokens 50000] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Launched plainly with --gpus N > 1 (no RANK in the environment) it re-executes itself under
@@ -26,6 +26,9 @@ Prints ONE JSON line (rank 0).  Extra objects:
   multi_gpu    (launcher runs) RCCL world size actually seen, per-rank ms_per_step min / max, gather_ms.
   cpu_baseline the CPU oracle (torch-CPU restatement of the reference, bf16 like the
                reference's default) timed on this box's host cores on a bounded sample.
+
+--dump-outputs DIR writes the logits of the last timed step as DIR/logits.npy (DIR/logits_rank<r>.npy with N > 1), float32, so
+that two builds can be compared output for output: weights and batch are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -45,12 +48,20 @@ _IMPORT_S = time.perf_counter() - _t_import
 
 PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA peak, MI355X_MICROARCH.md (measured 2495)
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all files of a run together (every rank's) stay below this
+
+
+def positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f'{s}: must be at least 1')
+    return v
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--steps', type=positive_int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--model', default='esm2_650m')
     ap.add_argument('--tokens', type=int, default=50000)
@@ -84,7 +95,12 @@ def parse():
                     help='replay the forward from a hipGraph (esme/graph.py); matters for small models / batches')
     ap.add_argument('--quantization', choices=['none', '4bit', '8bit'], default='none',
                     help="'4bit': layer projections resident in the esme-q4 format (not the headline config)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the logits of the last one to DIR/logits.npy (float32; a fixed row sample if larger '
+                         'than the size cap): the output to compare between two builds')
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error('--dump-outputs needs a real run: a --dry-run computes nothing')
     if args.precision is None:
         args.precision = 'high' if args.high_precision else 'fast'
     args.high_precision = args.precision == 'high'
@@ -104,6 +120,25 @@ def pmc_traffic(suffix=''):
         except Exception:
             continue
     return None, None
+
+
+def dump_outputs(dirname, name, y, budget):
+    """`y` (T, V) -> dirname/name.npy in float32 (exact for the bf16 and fp32 logits).  When the whole array exceeds `budget` bytes,
+    a sample of its rows is written instead: PCG64 seed 0, in row order, so runs with the same arguments keep the same rows.
+    Returns the line's note on what was written."""
+    import numpy as np
+    n = y.shape[0]
+    keep = min(n, max(1, budget // (4 * y.shape[1])))
+    rows = None
+    if keep < n:
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, keep, replace=False))
+        y = y[torch.from_numpy(rows).to(y.device)]
+    a = y.float().cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, name + '.npy')
+    np.save(path, a)
+    return {'file': path, 'shape': list(a.shape), 'dtype': str(a.dtype),
+            'rows': 'all' if rows is None else f'{keep} of {n} (seeded sample)'}
 
 
 def cpu_baseline(weights, heads, kind, L, E, seq_len, sample_tokens, gpu_logits=None, other_modes=None):
@@ -417,6 +452,10 @@ def main():
         fence()
         elapsed = time.perf_counter() - t0
     clock.mark('warmup_and_timed_steps')
+    dumped = None
+    if args.dump_outputs:                          # before anything else runs: a graph replay's `out` is a buffer the next replay overwrites
+        dumped = dump_outputs(args.dump_outputs, 'logits' if world == 1 else f'logits_rank{rank}', out, DUMP_BYTES // world - 4096)
+        clock.mark('dump_outputs')
     timed_s = elapsed
     step_ms = sorted(s.elapsed_time(e) for s, e in ev)
     multi = None
@@ -462,6 +501,8 @@ def main():
                 'frac_bf16_mfma_peak': round(flops_step / (ms_per_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4)},
     }
 
+    if dumped is not None:
+        result['dump_outputs'] = dumped
     if multi is not None:
         result['multi_gpu'] = multi
         if 'gather_ms' in multi:

@@ -29,6 +29,8 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(HERE))
+from golden_util import exact_cpu_gemms      # noqa: E402  (bf16 fields: GEMMs rounded once, the same on every CPU)
 REF = '/root/reference'
 
 
@@ -195,34 +197,38 @@ def main():
         rows = np.arange(tokens.numel()) if tap_rows is None else np.asarray(tap_rows)
         g['tap_rows'] = rows
         for dt, tag in ((torch.float32, 'f32'), (torch.bfloat16, 'bf16')):
-            model = build_ref_model(ref, syn, kind, L, E, H, seed, dt)
-            logits = model(tokens, (cu, max_len))
-            g[f'logits_{tag}'] = f32(logits)
-            g[f'logprob_{tag}'] = f32(model.predict_log_prob(tokens, (cu, max_len)))
-            rep = model.forward_representation(tokens, (cu, max_len))
-            g[f'rep_{tag}'] = f32(rep)[rows]
-            if layers_arg is not None:
-                g['layers_arg'] = np.asarray(layers_arg)
-                g[f'rep_layers_{tag}'] = f32(model.forward_representation(
-                    tokens, (cu, max_len), layers=list(layers_arg)))[rows]
-            if store_taps:
-                x0 = model.embedding(tokens) if kind == 'esm2' else model.embed_tokens(tokens)
-                g[f'emb_{tag}'] = f32(x0)[rows]
-                for name, t in layer_taps(model, x0, cu, max_len, 0).items():
-                    g[f'l0_{name}_{tag}'] = f32(t)[rows]
-            if with_padded:
-                # 2-D path: pad the same sequences to (B, max_len)
-                B = len(lengths)
-                tok2d = torch.full((B, max_len), 1, dtype=torch.int64)
-                for i, (a, b) in enumerate(zip(cu[:-1].tolist(), cu[1:].tolist())):
-                    tok2d[i, :b - a] = tokens[a:b]
-                g['tokens2d'] = tok2d.numpy()
-                g[f'logits2d_{tag}'] = f32(model(tok2d))
-                g[f'logprob2d_packedin_{tag}'] = f32(model.predict_log_prob(
-                    tokens, (cu, max_len), pad_output=True,
-                    pad_indices=torch.cat([torch.arange(i * max_len, i * max_len + (b - a))
-                                           for i, (a, b) in enumerate(zip(cu[:-1].tolist(), cu[1:].tolist()))])))
-        np.savez_compressed(os.path.join(HERE, fname), **g)
+            with exact_cpu_gemms(dt == torch.bfloat16):
+                model = build_ref_model(ref, syn, kind, L, E, H, seed, dt)
+                logits = model(tokens, (cu, max_len))
+                g[f'logits_{tag}'] = f32(logits)
+                g[f'logprob_{tag}'] = f32(model.predict_log_prob(tokens, (cu, max_len)))
+                rep = model.forward_representation(tokens, (cu, max_len))
+                g[f'rep_{tag}'] = f32(rep)[rows]
+                if layers_arg is not None:
+                    g['layers_arg'] = np.asarray(layers_arg)
+                    g[f'rep_layers_{tag}'] = f32(model.forward_representation(
+                        tokens, (cu, max_len), layers=list(layers_arg)))[rows]
+                if store_taps:
+                    x0 = model.embedding(tokens) if kind == 'esm2' else model.embed_tokens(tokens)
+                    g[f'emb_{tag}'] = f32(x0)[rows]
+                    for name, t in layer_taps(model, x0, cu, max_len, 0).items():
+                        g[f'l0_{name}_{tag}'] = f32(t)[rows]
+                if with_padded:
+                    # 2-D path: pad the same sequences to (B, max_len)
+                    B = len(lengths)
+                    tok2d = torch.full((B, max_len), 1, dtype=torch.int64)
+                    for i, (a, b) in enumerate(zip(cu[:-1].tolist(), cu[1:].tolist())):
+                        tok2d[i, :b - a] = tokens[a:b]
+                    g['tokens2d'] = tok2d.numpy()
+                    g[f'logits2d_{tag}'] = f32(model(tok2d))
+                    g[f'logprob2d_packedin_{tag}'] = f32(model.predict_log_prob(
+                        tokens, (cu, max_len), pad_output=True,
+                        pad_indices=torch.cat([torch.arange(i * max_len, i * max_len + (b - a))
+                                               for i, (a, b) in enumerate(zip(cu[:-1].tolist(), cu[1:].tolist()))])))
+        # the bf16 arrays in a companion file (golden_util.load_golden merges the two): each file stays under 1 MiB
+        bf16 = {k: v for k, v in g.items() if k.endswith('_bf16')}
+        np.savez_compressed(os.path.join(HERE, fname), **{k: v for k, v in g.items() if k not in bf16})
+        np.savez_compressed(os.path.join(HERE, fname[:-len('.npz')] + '_bf16.npz'), **bf16)
         return g
 
     run_model_fixture('g1_esm2_tiny.npz', 'esm2', 2, 64, 4, seed=11, lengths=[5, 26, 61],
@@ -233,15 +239,17 @@ def main():
     g2 = {'tokens': t2.numpy(), 'cu_lens': cu2.numpy(), 'max_len': ml2, 'seed': 8,
           'tokens2d': tokenize(readme, alphabet=Alphabet).numpy()}
     for dt, tag in ((torch.float32, 'f32'), (torch.bfloat16, 'bf16')):
-        model = build_ref_model(ref, syn, 'esm2', 6, 320, 20, 8, dt)
-        g2[f'logprob_{tag}'] = f32(model.predict_log_prob(t2, (cu2, ml2)))
-        g2[f'logprob2d_{tag}'] = f32(model.predict_log_prob(torch.from_numpy(g2['tokens2d'])))
+        with exact_cpu_gemms(dt == torch.bfloat16):
+            model = build_ref_model(ref, syn, 'esm2', 6, 320, 20, 8, dt)
+            g2[f'logprob_{tag}'] = f32(model.predict_log_prob(t2, (cu2, ml2)))
+            g2[f'logprob2d_{tag}'] = f32(model.predict_log_prob(torch.from_numpy(g2['tokens2d'])))
     # from_pretrained round trip through the reference loader on our checkpoint file
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         path = syn.write_checkpoint(os.path.join(td, '8M.safetensors'), 'esm2_8m', seed=8)
         m = ref.ESM.from_pretrained(path)
-        lp = m.predict_log_prob(t2, (cu2, ml2))
+        with exact_cpu_gemms():
+            lp = m.predict_log_prob(t2, (cu2, ml2))
         assert np.array_equal(bits(lp), g2['logprob_bf16']), 'from_pretrained != direct build'
     np.savez_compressed(os.path.join(HERE, 'g2_esm2_8m_readme.npz'), **g2)
 

@@ -69,7 +69,8 @@ def main():
     for dt, tag in ((torch.float32, 'f32'), (torch.bfloat16, 'bf16')):
         model = mg.build_ref_model(ref, syn, 'esmc', 2, 128, 2, 21, dt)
         for max_len, bs in ((None, 7), (20, 32)):
-            df = rv.predict_mask_margin(model, short, batch_size=bs, max_len=max_len)
+            with mg.exact_cpu_gemms(dt == torch.bfloat16):
+                df = rv.predict_mask_margin(model, short, batch_size=bs, max_len=max_len)
             g7['scores'].append(dict(dtype=tag, max_len=max_len, batch_size=bs, kind='esmc', L=2, E=128, H=2, seed=21,
                                      variants=list(df.index), score=[float(v) for v in df['score']]))
     with open(os.path.join(HERE, 'g7_variant.json'), 'w') as f:
@@ -139,9 +140,10 @@ def main():
             missing, unexpected = model.load_state_dict({k: v.to(dt) for k, v in sd.items()}, strict=True)
             assert not missing and not unexpected
             model.eval()
-            g10[f'{kind}_emb_{tag}'] = mg.f32(model.embedding(tokens, (cu, ml)))
-            g10[f'{kind}_logits_{tag}'] = mg.f32(model(tokens, (cu, ml)))
-            g10[f'{kind}_logits2d_{tag}'] = mg.f32(model(tok2d))
+            with mg.exact_cpu_gemms(dt == torch.bfloat16):
+                g10[f'{kind}_emb_{tag}'] = mg.f32(model.embedding(tokens, (cu, ml)))
+                g10[f'{kind}_logits_{tag}'] = mg.f32(model(tokens, (cu, ml)))
+                g10[f'{kind}_logits2d_{tag}'] = mg.f32(model(tok2d))
     np.savez_compressed(os.path.join(HERE, 'g10_esm1.npz'), **g10)
     # ---- G11 the reference's own row-wise int8 quantize / dequantize (esme/quantization.py:20-26)
     from esme.quantization import quantize as ref_quantize, dequantize as ref_dequantize

@@ -34,6 +34,25 @@ def test_bench_json_contract():
     assert c['kind'] == 'port' and c['unit'] == 'residues/s' and c['cores'] >= 1 and c['value'] > 0 and c['sample']
 
 
+def test_bench_dump_outputs_last_step_repeatable(tmp_path):
+    """--dump-outputs DIR: the (T, V) logits of the last timed step as float32, and --steps timed steps.  Weights and batch are seeded
+    and the forward has no atomics in its data path, so two runs with the same arguments write the same bits."""
+    import numpy as np
+    lines = []
+    for d in ('a', 'b'):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                              '--model', 'esm2_8m', '--tokens', '4096', '--seq-len', '256', '--no-cpu-baseline', '--no-half',
+                              '--dump-outputs', str(tmp_path / d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.strip().startswith('{')][0]))
+    a, b = np.load(tmp_path / 'a' / 'logits.npy'), np.load(tmp_path / 'b' / 'logits.npy')
+    assert a.shape == (4096, 33) and a.dtype == np.float32 and np.isfinite(a).all() and a.std() > 0
+    assert np.array_equal(a, b)
+    for d in lines:
+        assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['dump_outputs']['rows'] == 'all'
+        assert abs(d['value'] - 4096 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-3
+
+
 def test_bench_self_launch_rccl_world1():
     """`--spawn` forces the N>1 launcher path on this 1-GPU box: bench.py re-executes itself under
     torch.distributed.run, initialises RCCL (backend nccl) with world size 1 and must say so."""

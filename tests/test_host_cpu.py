@@ -442,6 +442,33 @@ def test_bench_refuses_world_size_mismatch():
     assert out.returncode != 0 and 'WORLD_SIZE=1' in out.stderr and '{' not in out.stdout
 
 
+def test_bench_refuses_zero_steps_and_dump_in_dry_run():
+    """--steps is the number of timed steps that ms_per_step divides by: 0 is refused, not a division by zero after the run.  A dry run
+    computes nothing, so there is nothing for --dump-outputs to write."""
+    out = _run_bench(['--steps', '0'])
+    assert out.returncode != 0 and 'must be at least 1' in out.stderr and '{' not in out.stdout
+    out = _run_bench(['--gpus', '2', '--dry-run', '--dump-outputs', 'unused'])
+    assert out.returncode != 0 and '--dump-outputs needs a real run' in out.stderr and '{' not in out.stdout
+
+
+def test_bench_dump_outputs_whole_or_seeded_row_sample(tmp_path):
+    """bench.dump_outputs: float32 values of the whole array when it fits the budget; above it, the same rows on every call (a seeded
+    sample, in row order), inside the budget."""
+    import bench
+    y = torch.randn(1000, 33, generator=torch.Generator().manual_seed(0)).bfloat16()
+    note = bench.dump_outputs(str(tmp_path / 'whole'), 'logits', y, 1 << 20)
+    a = np.load(tmp_path / 'whole' / 'logits.npy')
+    assert note['rows'] == 'all' and a.dtype == np.float32 and np.array_equal(a, y.float().numpy())
+    budget = 100 * 4 * 33
+    notes = [bench.dump_outputs(str(tmp_path / d), 'logits', y, budget) for d in ('a', 'b')]
+    a, b = np.load(tmp_path / 'a' / 'logits.npy'), np.load(tmp_path / 'b' / 'logits.npy')
+    assert notes[0]['rows'] == '100 of 1000 (seeded sample)' and a.shape == (100, 33) and np.array_equal(a, b)
+    assert a.nbytes <= budget
+    full = y.float().numpy()
+    idx = [int(np.flatnonzero((full == r).all(axis=1))[0]) for r in a]
+    assert idx == sorted(set(idx)) and len(idx) == 100
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='GPU boxes cover the self-launch path with RCCL (test_bench_contract_gpu.py)')
 def test_bench_self_launches_n_ranks_without_a_launcher():
     """`python bench.py --gpus 2` with no RANK in the environment re-executes itself under torch.distributed.run
