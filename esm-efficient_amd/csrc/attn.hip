@@ -1968,22 +1968,26 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
     // the 4-wave head-dim-64 kernel in its no-reference-maximum form
     const bool f16 = opts && opts->f16;                         // fp16 operands: speculative / defer-max passes bounded to fp16's range (see the kernels)
     const bool qp = opts && opts->q_prescaled;
-    ESME_CHECK_ARG(!(f16 && qp) || ((d == 64 || d == 32) && g_attn_variant != 1 && g_attn_variant != 2 && ld_o % 8 == 0 && aligned16(o)),
-                   "attn: fp16 operands combine with q_prescaled only in the ping-pong kernel (head dims 64 / 32: fixed reference 4, redo outside fp16's range)");
+    ESME_CHECK_ARG(!(f16 && qp) || ((d == 64 || d == 32) && ld_o % 8 == 0 && aligned16(o)),
+                   "attn: fp16 operands combine with q_prescaled for head dims 64 / 32 only (the ping-pong kernel's fixed-reference form; "
+                   "variants 1 / 2 and strides beyond 32-bit offsets run the generic kernel with a unit scale)");
+    // f16 + q_prescaled with variant 1 or 2: neither the first-generation nor the single-block kernel has the prescaled fp16 form, so these
+    // go to the generic kernel below with c = 1 (an exact-maximum online softmax in log2 units), as a stride that does not fit 32 bits does
+    const bool generic_qp16 = f16 && qp && (g_attn_variant == 1 || g_attn_variant == 2);
     AttnArgs a{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H,
                qp ? 1.0f : softmax_scale * 1.4426950408889634f, 1, H * B, exact ? 0.0f : g_attn_thr, exact ? 0 : g_attn_spec,
                opts ? opts->seq_order : nullptr};
     const hipStream_t s = (hipStream_t)stream;
     // (the ping-pong kernel addresses K / V with 32-bit byte offsets inside one sequence: (max_len + one tile) rows must fit)
     const bool fits32 = ((int64_t)max_len + KT) * ld_qkv * 2 < 0xffffffffLL;
-    if ((d == 64 || d == 32) && g_attn_variant == 2 && ld_o % 8 == 0 && aligned16(o) && fits32) {
+    if ((d == 64 || d == 32) && g_attn_variant == 2 && ld_o % 8 == 0 && aligned16(o) && fits32 && !generic_qp16) {
         // per-call option 2: the single-block pipelined kernel (attn_sb_kernel: 128 query rows per workgroup) -- what the q/k-pair entry runs; here for
         // A/B measurements of the plain forms against the ping-pong kernel
         AttnSplitArgs sa{a, 0, 0};
         if (d == 64) return f16 ? launch_sb<64, true, false, false>(sa, B, max_len, s) : (qp ? launch_sb<64, false, false, true>(sa, B, max_len, s) : launch_sb<64, false, false, false>(sa, B, max_len, s));
         return f16 ? launch_sb<32, true, false, false>(sa, B, max_len, s) : (qp ? launch_sb<32, false, false, true>(sa, B, max_len, s) : launch_sb<32, false, false, false>(sa, B, max_len, s));
     }
-    if (d == 64 && g_attn_variant != 1 && ld_o % 8 == 0 && aligned16(o) && fits32) {
+    if (d == 64 && g_attn_variant != 1 && ld_o % 8 == 0 && aligned16(o) && fits32 && !generic_qp16) {
         // head dim 64 (ESM2-650M / 3B, ESM-C): the software-pipelined kernel.  4 waves = 256 query rows per workgroup, two
         // workgroups per CU (one's prologue / epilogue overlaps the other's main loop): measured faster than 8 waves
         // (one workgroup per CU) from S = 130 to S = 2 000; the 8-wave form stays behind the tuning hook.
@@ -1995,7 +1999,7 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
         if (qp && nw == 4) return launch_pp64<4, true>(a, B, max_len, s);
         return nw == 8 ? launch_pp64<8>(a, B, max_len, s) : launch_pp64<4>(a, B, max_len, s);
     }
-    if (d == 32 && g_attn_variant != 1 && ld_o % 8 == 0 && aligned16(o) && fits32) {
+    if (d == 32 && g_attn_variant != 1 && ld_o % 8 == 0 && aligned16(o) && fits32 && !generic_qp16) {
         // head dim 32 (ESM2-150M; ESM2-35M's padded heads): the same software-pipelined kernel at D = 32 (round 4)
         if (f16) return qp ? launch_pp64<4, true, 32, true>(a, B, max_len, s) : launch_pp64<4, false, 32, true>(a, B, max_len, s);
         return qp ? launch_pp64<4, true, 32>(a, B, max_len, s) : launch_pp64<4, false, 32>(a, B, max_len, s);

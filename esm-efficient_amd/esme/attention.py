@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from esme import _hip
-from esme.nn import GELU, LayerNorm, Linear
+from esme.nn import GELU, LayerNorm, Linear, weights_epoch
 from esme.rotary import RotaryEmbedding
 
 # head dim 64 / 32 with fused rotary: softmax_scale * log2(e) folded into q by the QKV epilogue, attention without a reference maximum
@@ -107,7 +107,9 @@ def _pad_rows(t: torch.Tensor, n: int) -> torch.Tensor:
 
 
 def _version_key(*params):
-    return tuple((p.data_ptr(), p._version) for p in params if p is not None)
+    """Cache key of a copy derived from `params`: their addresses and version counters, and the weight-edit epoch (esme.nn.weights_epoch: moved
+    by ESM2.invalidate_graphs after in-place writes that bump no version counter)."""
+    return (weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in params if p is not None)
 
 
 def _check_fp16_range(w16: torch.Tensor) -> None:
@@ -189,16 +191,30 @@ class HalfGuard:
             is most visible), row 1 + 2 i after layer i's attention branch, row 2 + 2 i after its FFN branch -- of the STORED stream, i.e. times
             the column scaling of the LayerNorm that reads it next (ESM2._guard_scales undoes it);
       qk    (L, 2, heads): max over rows of the squared row norm of q (then k) per head, for layers whose q / k are single fp16 values and whose
-            rotary is fused into the projection (ESM-2 / ESM-1 blocks; zeros elsewhere: not covered).
+            rotary is fused into the projection (ESM-2 / ESM-1 blocks) or pass through ESM-C's q / k pass (zeros elsewhere: not covered).
+      q_scaled  the unit of qk[:, 0]: True when its q norms carry softmax_scale * log2(e) squared -- the LN-folded projection records q AFTER
+            its q_scale (HalfPlan.qp on an ESM-2 block), ESM-C's q / k pass before it.  `rescale_q` converts the maxima when a plan of the
+            other unit takes over, so that maxima of forwards under different plans stay comparable.
     Sticky across forwards until `clear()`; ESM2.check_plan reads them at a synchronisation point."""
 
     def __init__(self, n_layers: int, phys_dim: int, heads: int, device):
         self.col = torch.zeros(2 * n_layers + 1, phys_dim, dtype=torch.int32, device=device)
         self.qk = torch.zeros(n_layers, 2, heads, dtype=torch.int32, device=device)
+        self.q_scaled = False
 
     def clear(self):
         self.col.zero_()
         self.qk.zero_()
+        return self
+
+    def rescale_q(self, q_scaled: bool, q_scale: float):
+        """Bring the recorded q norms into the unit of forwards whose projection does (`q_scaled`) or does not multiply q by `q_scale`:
+        one in-place multiply on the device (no synchronisation); nothing when the unit is unchanged."""
+        q_scaled = bool(q_scaled)
+        if q_scaled != self.q_scaled:
+            s2 = float(q_scale) ** 2
+            self.qk.view(torch.float32)[:, 0].mul_(s2 if q_scaled else 1.0 / s2)
+            self.q_scaled = q_scaled
         return self
 
 

@@ -133,7 +133,8 @@ class ESM2(nn.Module):
         w = self.embed_tokens.weight
         if not self.padded:
             return w
-        key = (w.data_ptr(), w._version)
+        from esme.attention import _version_key
+        key = _version_key(w)
         if key != self._embed_pad_key:
             from esme.attention import _pad_last
             with torch.no_grad():
@@ -214,7 +215,7 @@ class ESM2(nn.Module):
             self._half_calib = (tokens.detach().reshape(-1).cpu().to(torch.int64), cu.detach().reshape(-1).cpu().to(torch.int32))
             self._half_plan, changed = None, True
         if changed:
-            self.invalidate_graphs()
+            self._drop_derived()                              # (keeps the plan just decided on; invalidate_graphs() would recalibrate)
         return self
 
     def half_plan(self, device=None):
@@ -281,9 +282,9 @@ class ESM2(nn.Module):
         ratio = torch.where(med[:, None] > 0, x / med[:, None].clamp_min(1e-30), torch.zeros_like(x)).amax(dim=0)
         qk = guard.qk.view(torch.float32)
         att = self.layers[0].self_attn
-        # (HalfPlan.qp with the rotary fused into the projection: the epilogue's guard sees q AFTER softmax_scale * log2(e) went in; ESM-C's q/k pass measures before)
-        prescaled = bool(getattr(getattr(self, '_half_plan', None), 'qp', False)) and not att.pre_layernorm
-        bound = (qk[:, 0] * qk[:, 1]).sqrt().amax(dim=1) * ((1.0 / 1.4426950408889634) if prescaled else att.head_dim ** -0.5)
+        # the unit the q norms were RECORDED in (HalfGuard.q_scaled), not the current plan's: a plan change between the forwards and this reading
+        # would otherwise mis-scale the bound by softmax_scale * log2(e)
+        bound = (qk[:, 0] * qk[:, 1]).sqrt().amax(dim=1) * ((1.0 / 1.4426950408889634) if guard.q_scaled else att.head_dim ** -0.5)
         return ratio, bound, qk.amax(dim=(1, 2)) > 0
 
     def _calibrate_half(self, device):
@@ -343,14 +344,19 @@ class ESM2(nn.Module):
         return HalfPlan(sel, qk_pair, info, qk_layers=flags, site_ref=self._last_site_median.clone(), qp=qp)
 
     # -- the plan checked against the data (round 6) -----------------------------------------------------------------------
-    def _guard_buffers(self, device):
-        """The model's HalfGuard (created with the first 'half' forward on `device`; None when half_guard is off)."""
+    def _guard_buffers(self, device, plan=None):
+        """The model's HalfGuard (created with the first 'half' forward on `device`; None when half_guard is off), its q norms in the unit the
+        forwards of `plan` record them in (HalfGuard.q_scaled: the LN-folded projection of an ESM-2 block records q after the plan's q scale)."""
         if not self.half_guard or not len(self.layers):
             return None
         g = getattr(self, '_half_guard', None)
         if g is None or g.col.device != torch.device(device) or g.col.shape != (2 * len(self.layers) + 1, self.phys_dim):
             from esme.attention import HalfGuard
             g = self._half_guard = HalfGuard(len(self.layers), self.phys_dim, self.layers[0].self_attn.num_heads, device)
+        if plan is not None and not torch.cuda.is_current_stream_capturing():      # (a capture follows warm-up forwards of the same plan)
+            from esme.attention import _q_scale
+            att = self.layers[0].self_attn
+            g.rescale_q(plan.qp and not att.pre_layernorm, _q_scale(att.head_dim))
         return g
 
     def _plan_masks(self, plan, dev):
@@ -386,7 +392,9 @@ class ESM2(nn.Module):
 
     def _plan_verdict(self, vec, update: bool = True, where: str = ''):
         """Host-side half of check_plan: `vec` = a _guard_snapshot() on the host.  None when the plan held; else the verdict dict (and, with
-        `update`, the widened plan installed)."""
+        `update`, the widened plan installed).  What no plan can cover (more than 64 massive channels; large scores in a block without a q/k-pair
+        form) leaves the plan, its descriptors and graphs as they are: with `update` it is recorded in plan.info['uncovered'] and warned about once
+        per plan; without, nothing is written (and the warning repeats until an updating check has recorded it)."""
         if vec is None or float(vec[0]) == 0.0:
             return None
         E, L = self.embed_dim, len(self.layers)
@@ -409,28 +417,46 @@ class ESM2(nn.Module):
                f"{max([r for _, r in chans], default=0):.1f}x the median channel (threshold {self.HALF_CHANNEL_RATIO}), "
                f"{len(layers)} layer(s) without q/k pairs reach a score bound of {max([b for _, b in layers], default=0):.0f} (threshold {self.HALF_SCORE_BOUND}); "
                "results computed since the last check may miss the mode's 1e-3.")
-        if update:
+        # the widest plan that could cover this: the current selection stays, offenders join (largest first, up to 64); offending layers get pairs where the block has them
+        merged = torch.where(sel_mask, torch.full_like(ratio, float('inf')), ratio)
+        cand = torch.nonzero(sel_mask | bad_c).flatten()
+        if cand.numel() > 64:
+            cand = cand[torch.argsort(merged[cand], descending=True)[:64]]
+        cand = torch.sort(cand).values
+        new_flags = [bool(f) or (pair_ok and bool(b)) for f, b in zip(flags.tolist(), bad_l.tolist())]
+        new_mask = torch.zeros(E, dtype=torch.bool)
+        new_mask[cand] = True
+        left = ([c for c, _ in chans if not bool(new_mask[c])], [i for i, _ in layers if not new_flags[i]])
+        if left[0] or left[1]:
+            verdict['uncovered'] = True
+        widens = tuple(cand.tolist()) != tuple(plan.ext_key or ()) or new_flags != flags.tolist()
+        if not widens:
+            # nothing a plan can do about these offenders: the plan stays (no re-run, no new descriptor or graph); say so once per plan
+            seen = plan.info.get('uncovered', {'channels': [], 'layers': []})
+            new = [c for c in left[0] if c not in seen['channels']], [i for i in left[1] if i not in seen['layers']]
+            if update:                                            # (a read-only check does not touch the plan: it warns until an updating one records)
+                plan.info['uncovered'] = {'channels': sorted(seen['channels'] + new[0]), 'layers': sorted(seen['layers'] + new[1])}
+            if not (new[0] or new[1]):
+                verdict['message'] = msg + " (The plan cannot cover this: warned about once for this plan.)"
+                return verdict
+            msg += (" The plan cannot cover this (more than 64 massive channels, or large scores in a block without a q/k-pair form) and stays as it is; "
+                    "use precision 'exact' if 1e-3 must hold.  (Said once per plan.)")
+        elif update:
             from esme.attention import HalfPlan
             dev = self.embed_tokens.weight.device
-            merged = torch.where(sel_mask, torch.full_like(ratio, float('inf')), ratio)        # the current selection stays; offenders join, largest first
-            cand = torch.nonzero(sel_mask | bad_c).flatten()
-            full = cand.numel() > 64
-            if full:
-                cand = cand[torch.argsort(merged[cand], descending=True)[:64]]
-            sel = torch.sort(cand).values.to(torch.int32).contiguous().to(dev) if cand.numel() else None
-            new_flags = [bool(f) or (pair_ok and bool(b)) for f, b in zip(flags.tolist(), bad_l.tolist())]
+            sel = cand.to(torch.int32).contiguous().to(dev) if cand.numel() else None
             info = dict(plan.info)
             info['updates'] = info.get('updates', 0) + 1
             info['massive_channels'] = int(cand.numel())
             info['qk_pair_layers'] = sum(new_flags) if pair_ok else 0
+            info['uncovered'] = {'channels': sorted(left[0]), 'layers': sorted(left[1])}      # (already said below: not repeated for this plan)
             self._half_plan = HalfPlan(sel, pair_ok and any(new_flags), info, qk_layers=new_flags if pair_ok else None, site_ref=plan.site_ref, qp=plan.qp)
-            self.invalidate_graphs()
+            self._drop_derived()
             verdict['updated'] = True
             msg += " The plan was widened (" + self._half_plan.describe() + "): re-run the batch."
-            if full or (layers and not pair_ok):
+            if verdict.get('uncovered'):
                 msg += (" It cannot cover everything (more than 64 massive channels, or large scores in a block without a q/k-pair form): "
                         "use precision 'exact' if 1e-3 must hold.")
-                verdict['uncovered'] = True
         verdict['message'] = msg
         import warnings
         warnings.warn(msg, RuntimeWarning, stacklevel=3)
@@ -445,7 +471,12 @@ class ESM2(nn.Module):
         offending layers get q / k pairs where the block has that form), so that the NEXT forward is covered -- re-run the batch that tripped it
         (predict_log_prob / predict_prob do that themselves).  A RuntimeWarning accompanies every stale verdict.  Coverage: the channel check runs
         in every residual epilogue of every model; the score check in the LayerNorm-folded projections with fused rotary (ESM-2 family, head
-        dims 16 / 32 / 64) and in ESM-C's q / k LayerNorm + rotary pass -- ESM-1b / 1v (no rotary) and head dim 128 rely on the calibration for it."""
+        dims 16 / 32 / 64) and in ESM-C's q / k LayerNorm + rotary pass -- ESM-1b / 1v (no rotary) and head dim 128 rely on the calibration for it.
+        The maxima carry the unit of q they were recorded in (HalfGuard.q_scaled: the projection records q after the fixed-reference form's
+        q scale, ESM-C's pass before it) and are converted when a plan of the other unit runs, so a plan change between the forwards and this
+        check reads the same bound.  A verdict no plan can cover (more than 64 massive channels; large scores in a block without a q/k-pair
+        form) returns 'updated': False, 'uncovered': True and changes nothing -- no new plan, no new descriptor or graph, no re-run in
+        predict_* -- and warns once per plan.  After editing weights in place, invalidate_graphs() drops the plan: the next forward recalibrates."""
         vec = self._guard_snapshot()
         if vec is None:
             return None
@@ -454,14 +485,12 @@ class ESM2(nn.Module):
     def _apply(self, fn, *a, **kw):
         """`.to()`, `.cuda()`, dtype casts: the parameters' storage moves -- drop everything derived from it."""
         out = super()._apply(fn, *a, **kw)
-        self._half_plan = None                # (its channel list lives on the old device; recalibrated on first use)
-        self.invalidate_graphs()
+        self.invalidate_graphs()              # (drops the plan too: its channel list lives on the old device; recalibrated on first use)
         return out
 
     def load_state_dict(self, *a, **kw):
         out = super().load_state_dict(*a, **kw)
-        self._half_plan = None                # other weights, other plan
-        self.invalidate_graphs()
+        self.invalidate_graphs()              # (drops the plan too: other weights, other plan)
         return out
 
     # -- helpers ---------------------------------------------------------------
@@ -482,7 +511,7 @@ class ESM2(nn.Module):
         ctx.probe = getattr(self, '_calib_probe', None)
         if self.precision == 'half':
             ctx.ovf = self._overflow_flag(device)
-            ctx.guard = getattr(self, '_half_guard', None) if getattr(self, '_calib_probe', None) is not None else self._guard_buffers(device)
+            ctx.guard = getattr(self, '_half_guard', None) if getattr(self, '_calib_probe', None) is not None else self._guard_buffers(device, plan)
         return ctx
 
     # -- run-time range guard of precision 'half' --------------------------------------------------------------------
@@ -693,7 +722,8 @@ class ESM2(nn.Module):
         if self.precision != 'half' or self.half_check != 'sync' or getattr(self, '_defer_overflow', False) or torch.cuda.is_current_stream_capturing():
             return y
         self.check_overflow()
-        if self.check_plan(update=True) is not None:
+        v = self.check_plan(update=True)
+        if v is not None and v['updated']:                    # (a verdict no plan can cover changes nothing: no re-run)
             y = run()
             self.check_overflow()
             self.check_plan(update=False)                     # (whatever is left cannot be covered: warned about, not looped on)
@@ -712,21 +742,33 @@ class ESM2(nn.Module):
         """`getattr(self, what)(tokens, pad_args)` replayed from a hipGraph captured on first use of this
         input shape (esme/graph.py).  For repeated shapes of small batches, where ~160 Python-issued launches
         cost more than the GPU work.  With `clone=False` the result is a static buffer that the next replay of
-        the same shape overwrites."""
+        the same shape overwrites.  'predict_log_prob' in precision 'half' with half_check = 'sync' checks the token ids, the range flag and the
+        plan after each replay, as the eager call does (a widened plan is re-captured and replayed once)."""
         assert what in ('forward', 'forward_representation', 'predict_log_prob')
         if getattr(self, '_graph_cache', None) is None:
             from esme.graph import GraphCache
             self._graph_cache = GraphCache(self)
-        y = self._graph_cache.run(what, tokens, pad_args, clone)
+        y = self._graph_cache.run(what, tokens, pad_args, clone)        # (a capture warms up with the checks deferred: esme.graph)
         if what == 'predict_log_prob' and self.precision == 'half' and self.half_check == 'sync' and not getattr(self, '_defer_overflow', False):
-            self.check_overflow()           # (skipped while capturing; a replay sets the same sticky flags the eager call checks)
-            if self.check_plan(update=True) is not None:          # (the widened plan dropped the captured graphs: this call captures anew)
+            self.check_tokens(tokens)       # (as eager predict_log_prob does; the capture's warm-up runs with the checks deferred)
+            self.check_overflow()           # (once, after the replay: it sets the same sticky flags the eager call checks)
+            v = self.check_plan(update=True)
+            if v is not None and v['updated']:                    # (the widened plan dropped the captured graphs: this call captures anew)
                 y = self._graph_cache.run(what, tokens, pad_args, clone)
         return y
 
     def invalidate_graphs(self):
-        """Forget captured hipGraphs and the C-entry model descriptor (after changing weights in place, in particular
-        through `p.data`, which bumps no version counter)."""
+        """Forget captured hipGraphs, the C-entry model descriptor AND the calibrated HalfPlan of precision 'half' -- call it after changing
+        weights in place, in particular through `p.data`, which bumps no version counter: the next 'half' forward recalibrates on the
+        edited weights (a plan decided on the old ones would keep their massive channels and score bounds), and every derived weight copy
+        (LN-folded, fp16, extension-tile, packed, padded) is rebuilt from them on next use."""
+        from esme.nn import bump_weights_epoch
+        self._half_plan = None
+        bump_weights_epoch()                  # every derived weight copy is rebuilt on next use (its key holds the epoch: esme.attention._version_key)
+        self._drop_derived()
+
+    def _drop_derived(self):
+        """invalidate_graphs() without the plan: what set_precision / a widening plan verdict call after installing the plan they decided on."""
         if getattr(self, '_graph_cache', None) is not None:
             self._graph_cache.clear()
         self.__dict__.pop('_cdesc', None)

@@ -68,20 +68,31 @@ class GraphedForward:
         self._keep = None           # strong references to everything captured from outside the graph's pool
 
     def _capture(self):
-        side = torch.cuda.Stream(device=self.tokens.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(2):          # builds packed / folded weights, rotary tables, kernel attributes
-                self.fn(self.tokens, (self.cu_lens, self.max_len))
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        guard = getattr(self.model, '_half_guard', None)
-        if guard is not None:
-            guard.clear()               # the warm-up forwards ran on placeholder tokens (all id 0): not data the plan should be held to
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph), torch.no_grad():
-            self.out = self.fn(self.tokens, (self.cu_lens, self.max_len))
-        self._keep = external_tensors(self.model)      # e.g. the rotary tables of THIS max_len survive a later regrow
+        # run() has copied the caller's batch into the static buffers: the warm-up forwards run on it, and what the plan guard
+        # (esme.attention.HalfGuard) records there is data like any other -- merged into the running maxima, not cleared, so that a
+        # stale plan seen by an earlier unchecked forward is still reported by the next check.  The inline checks of precision 'half'
+        # (predict_log_prob's) are deferred meanwhile: a plan widened between warm-up and capture would clear this very entry from the
+        # cache; the caller (ESM2.graphed) checks once after the first replay instead.
+        model = self.model
+        deferred = model.__dict__.get('_defer_overflow', None)
+        model._defer_overflow = True
+        try:
+            side = torch.cuda.Stream(device=self.tokens.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side), torch.no_grad():
+                for _ in range(2):          # builds packed / folded weights, rotary tables, kernel attributes
+                    self.fn(self.tokens, (self.cu_lens, self.max_len))
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph), torch.no_grad():
+                self.out = self.fn(self.tokens, (self.cu_lens, self.max_len))
+        finally:
+            if deferred is None:
+                model.__dict__.pop('_defer_overflow', None)
+            else:
+                model._defer_overflow = deferred
+        self._keep = external_tensors(model)           # e.g. the rotary tables of THIS max_len survive a later regrow
         self.graph = graph
 
     def run(self, tokens: torch.Tensor, cu_lens: torch.Tensor, clone: bool = True) -> torch.Tensor:

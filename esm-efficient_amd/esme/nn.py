@@ -28,6 +28,20 @@ def param_epoch() -> int:
     return _EPOCH[0]
 
 
+# Weight-edit epoch: bumped by ESM2.invalidate_graphs() (and so by load_state_dict / `.to()`), the documented step after writing weights in place --
+# through `p.data` in particular, which moves no version counter.  esme.attention._version_key mixes it into EVERY derived-weight cache key (LN-folded,
+# fp16, extension-tile, packed, padded copies), so that no cache can be left out of an invalidation.  Global: another model's caches rebuild once too.
+_WEIGHTS_EPOCH = [0]
+
+
+def bump_weights_epoch() -> None:
+    _WEIGHTS_EPOCH[0] += 1
+
+
+def weights_epoch() -> int:
+    return _WEIGHTS_EPOCH[0]
+
+
 class _TrackedModule(nn.Module):
     def __setattr__(self, name, value):
         if name in ('weight', 'bias'):

@@ -212,10 +212,11 @@ typedef struct esme_attn_opts {
     int q_prescaled;
     int f16;                     /* != 0: q, k, v and o are IEEE fp16 (precision 'half').  P is fp16 as well: the speculative pass keeps its first-tile
                                   * reference maximum and redoes a work item with exact maxima when a P would leave fp16's range.  With q_prescaled
-                                  * (ABI 10; head dims 64 / 32, the ping-pong kernel): the no-reference form with a FIXED reference of 4 (log2 units) --
+                                  * (ABI 10; head dims 64 / 32 only, else BAD_ARG): the ping-pong kernel's no-reference form with a FIXED reference of 4 (log2 units) --
                                   * the score accumulators start at -4.0, P = 2^(score - 4) stays inside fp16 for scores up to 20 (13.9 natural units);
                                   * a work item with a higher score, or with a row whose sum falls below S * 2^-14 (its P values average below fp16's smallest normal), is redone
-                                  * with exact maxima: always correct, fast where a model's scores stay inside that window */
+                                  * with exact maxima: always correct, fast where a model's scores stay inside that window.  Variants 1 and 2, and a row stride for which
+                                  * (max_len + 64) rows do not fit 32-bit byte offsets, run the generic kernel with a unit scale instead (online softmax in log2 units) */
 } esme_attn_opts_t;
 int esme_hip_attn_varlen_fwd_opts(const void* q, const void* k, const void* v, int64_t ld_qkv,
                                   void* o, int64_t ld_o, const int32_t* cu_lens, int B, int64_t T,
@@ -427,7 +428,10 @@ typedef struct esme_gemm_fusion {
      *       the STORED stream (= rho_out[n] * x: divide by pair_scale_out to compare channels).  Non-negative floats order like their bit
      *       patterns; inf / NaN stick on top.
      *   qk_sumsq (uint32 (2, H), f16 + LN fold + fused rotary without pair output only; H = rot_cols / 2 / head_dim): [0][h] = float bits of
-     *       max_m sum_c q[m, h, c]^2 after rotation, [1][h] the same for k: sqrt(q2 k2) * softmax_scale bounds |score| of head h. */
+     *       max_m sum_c q[m, h, c]^2 after rotation, [1][h] the same for k, both of the STORED fp16 values: sqrt(q2 k2) * softmax_scale bounds
+     *       |score| of head h.  With q_scale != 0 the stored q carries q_scale, and so does [0][h] (q_scale^2 times the unscaled norm:
+     *       sqrt(q2 k2) / log2(e) is then the bound); esme_hip_qk_norm_rotary_f16_scaled records q BEFORE its scale.  A caller that mixes
+     *       both kinds of launch into one buffer converts between them (esme.attention.HalfGuard.q_scaled). */
     uint32_t* col_absmax;
     uint32_t* qk_sumsq;
 } esme_gemm_fusion_t;
