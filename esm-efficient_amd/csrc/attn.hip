@@ -1947,6 +1947,25 @@ static int launch_w4(AttnArgs& a, int B, int max_len, hipStream_t s) {
 
 #endif
 
+// The generic and split kernels take the sequence from grid z (at most 65 535 per launch: more run as several launches) and address
+// rows inside one sequence with 32-bit element offsets (row * ld_qkv + column, row < max_len + one row tile).  Checked before any launch:
+// a stride for which that product passes 2^32 elements is refused, and so is a dispatch order with more sequences than one launch holds
+// (the chunks advance cu_lens, which an order into the whole batch would then mis-index; callers pass one only for B <= 1 024).
+static constexpr int kMaxGridZ = 65535;
+
+static int generic_launch_ok(int64_t ld_qkv, int max_len, int rows, int B, const int32_t* seq_order, const char* what) {
+    if (((int64_t)max_len + rows) * ld_qkv >= (1LL << 32)) {
+        snprintf(error_buffer(), kErrorBufferSize, "%s: (max_len + %d) * ld_qkv must stay below 2^32 elements (32-bit row offsets "
+                 "inside one sequence)", what, rows);
+        return ESME_ERR_UNSUPPORTED;
+    }
+    if (seq_order && B > kMaxGridZ) {
+        snprintf(error_buffer(), kErrorBufferSize, "%s: seq_order is not supported with more than 65535 sequences", what);
+        return ESME_ERR_ARG;
+    }
+    return ESME_OK;
+}
+
 // (per-call options, esme_attn_opts_t: no process-global tuning state; NULL = the defaults below)
 static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv, void* o, int64_t ld_o, const int32_t* cu_lens,
                     int B, int64_t T, int H, int d, int max_len, float softmax_scale, void* stream, bool exact,
@@ -1963,14 +1982,14 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
                    "attn: bad row strides");
     ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0,
                    "attn: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && B <= 65535, "attn: max_len must be > 0, H and B <= 65535");
+    ESME_CHECK_ARG(max_len > 0 && H <= 65535, "attn: max_len must be > 0, H <= 65535");
     // q_prescaled: q already carries softmax_scale * log2(e) (esme_gemm_fusion_t.q_scale): every kernel then runs with c = 1, and
     // the 4-wave head-dim-64 kernel in its no-reference-maximum form
     const bool f16 = opts && opts->f16;                         // fp16 operands: speculative / defer-max passes bounded to fp16's range (see the kernels)
     const bool qp = opts && opts->q_prescaled;
     ESME_CHECK_ARG(!(f16 && qp) || ((d == 64 || d == 32) && ld_o % 8 == 0 && aligned16(o)),
                    "attn: fp16 operands combine with q_prescaled for head dims 64 / 32 only (the ping-pong kernel's fixed-reference form; "
-                   "variants 1 / 2 and strides beyond 32-bit offsets run the generic kernel with a unit scale)");
+                   "variants 1 / 2, and strides for which (max_len + 64) rows pass 2^32 bytes, run the generic kernel with a unit scale)");
     // f16 + q_prescaled with variant 1 or 2: neither the first-generation nor the single-block kernel has the prescaled fp16 form, so these
     // go to the generic kernel below with c = 1 (an exact-maximum online softmax in log2 units), as a stride that does not fit 32 bits does
     const bool generic_qp16 = f16 && qp && (g_attn_variant == 1 || g_attn_variant == 2);
@@ -2009,28 +2028,38 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
     const int qb = (g_force_qb ? g_force_qb : (max_len >= 192 ? 2 : 1));
     const bool two = qb == 2 && d <= 64;
     const int rows = QT * (two ? 2 : 1);
-    const dim3 grid((unsigned int)((max_len + rows - 1) / rows), (unsigned int)H, (unsigned int)B), block(256);
+    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn: head dim must be 16, 32, 64 or 128");
+    if (const int rc = generic_launch_ok(ld_qkv, max_len, rows, B, a.order, "attn")) return rc;
+    const hipStream_t s0 = s;
+    // sequence index on grid z (at most 65 535): chunks of sequences, each with cu_lens advanced to its first sequence
+    for (int b0 = 0; b0 < B; b0 += kMaxGridZ) {
+        const int nb = B - b0 < kMaxGridZ ? B - b0 : kMaxGridZ;
+        AttnArgs ac = a;
+        ac.cu = cu_lens + b0;
+        ac.nhb = H * nb;
+        const dim3 grid((unsigned int)((max_len + rows - 1) / rows), (unsigned int)H, (unsigned int)nb), block(256);
 #define ESME_ATTN(DD)                                                                         \
     case DD:                                                                                   \
         if (f16) {                                                                             \
-            if (two) hipLaunchKernelGGL((attn_varlen_kernel<DD, (DD <= 64 ? 2 : 1), true>), grid, block, 0, s, a); \
-            else hipLaunchKernelGGL((attn_varlen_kernel<DD, 1, true>), grid, block, 0, s, a);  \
-        } else if (two) hipLaunchKernelGGL((attn_varlen_kernel<DD, (DD <= 64 ? 2 : 1)>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((attn_varlen_kernel<DD, 1>), grid, block, 0, s, a);            \
+            if (two) hipLaunchKernelGGL((attn_varlen_kernel<DD, (DD <= 64 ? 2 : 1), true>), grid, block, 0, s0, ac); \
+            else hipLaunchKernelGGL((attn_varlen_kernel<DD, 1, true>), grid, block, 0, s0, ac);  \
+        } else if (two) hipLaunchKernelGGL((attn_varlen_kernel<DD, (DD <= 64 ? 2 : 1)>), grid, block, 0, s0, ac); \
+        else hipLaunchKernelGGL((attn_varlen_kernel<DD, 1>), grid, block, 0, s0, ac);            \
         break;
-    switch (d) {
-        ESME_ATTN(16)
-        ESME_ATTN(32)
-        ESME_ATTN(64)
-        ESME_ATTN(128)
-        default: ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn: head dim must be 16, 32, 64 or 128");
-    }
+        switch (d) {
+            ESME_ATTN(16)
+            ESME_ATTN(32)
+            ESME_ATTN(64)
+            ESME_ATTN(128)
+        }
 #undef ESME_ATTN
-    return check_launch("attn_varlen_fwd");
+        if (const int rc = check_launch("attn_varlen_fwd")) return rc;
+    }
+    return ESME_OK;
 }
 
 template <int D, bool F16 = false, bool QKP = false>
-static int launch_split(const AttnSplitArgs& sa, const dim3 grid, hipStream_t s) {
+static int launch_split(const AttnSplitArgs& sa, int B, int max_len, hipStream_t s) {
     constexpr int smem = 2 * (2 * KT * D * 2 + (QKP ? 1 : 2) * D * 128);
     auto kern = attn_split_kernel<D, F16, QKP>;
     if (smem >= 64 * 1024) {
@@ -2044,8 +2073,17 @@ static int launch_split(const AttnSplitArgs& sa, const dim3 grid, hipStream_t s)
             done.fetch_or(bit, std::memory_order_release);
         }
     }
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, sa);
-    return check_launch("attn_varlen_fwd_split");
+    // sequence index on grid z (at most 65 535): chunks of sequences, each with cu_lens advanced to its first sequence
+    for (int b0 = 0; b0 < B; b0 += kMaxGridZ) {
+        const int nb = B - b0 < kMaxGridZ ? B - b0 : kMaxGridZ;
+        AttnSplitArgs sc = sa;
+        sc.a.cu = sa.a.cu + b0;
+        sc.a.nhb = sa.a.H * nb;
+        const dim3 grid((unsigned int)((max_len + QT - 1) / QT), (unsigned int)sa.a.H, (unsigned int)nb);
+        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, sc);
+        if (const int rc = check_launch("attn_varlen_fwd_split")) return rc;
+    }
+    return ESME_OK;
 }
 
 extern "C" int esme_hip_attn_varlen_fwd_split(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t lo_qkv, void* o,
@@ -2057,16 +2095,17 @@ extern "C" int esme_hip_attn_varlen_fwd_split(const void* q, const void* k, cons
     ESME_CHECK_ARG(ld_qkv % 8 == 0 && lo_qkv % 8 == 0 && lo_qkv > 0 && ld_o % 4 == 0 && lo_o % 4 == 0 && lo_o >= (int64_t)H * d &&
                    ld_o >= lo_o + (int64_t)H * d, "attn_split: bad row strides / pair offsets");
     ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0, "attn_split: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && B <= 65535, "attn_split: max_len must be > 0, H and B <= 65535");
+    ESME_CHECK_ARG(max_len > 0 && H <= 65535, "attn_split: max_len must be > 0, H <= 65535");
+    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_split: head dim must be 16, 32, 64 or 128");
+    if (const int rc = generic_launch_ok(ld_qkv, max_len, QT, B, seq_order, "attn_split")) return rc;
     AttnSplitArgs sa{{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H, softmax_scale * 1.4426950408889634f, 1, H * B,
                       0.0f, 0, seq_order}, lo_qkv, lo_o};
-    const dim3 grid((unsigned int)((max_len + QT - 1) / QT), (unsigned int)H, (unsigned int)B);
     const hipStream_t s = (hipStream_t)stream;
     switch (d) {
-        case 16: return launch_split<16>(sa, grid, s);
-        case 32: return launch_split<32>(sa, grid, s);
-        case 64: return launch_split<64>(sa, grid, s);
-        case 128: return launch_split<128>(sa, grid, s);
+        case 16: return launch_split<16>(sa, B, max_len, s);
+        case 32: return launch_split<32>(sa, B, max_len, s);
+        case 64: return launch_split<64>(sa, B, max_len, s);
+        case 128: return launch_split<128>(sa, B, max_len, s);
         default: ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_split: head dim must be 16, 32, 64 or 128");
     }
 }
@@ -2081,20 +2120,21 @@ extern "C" int esme_hip_attn_varlen_fwd_qkpair_f16_opts(const void* q, const voi
     ESME_CHECK_ARG(q && k && v && o && cu_lens, "attn_qkpair: null pointer");
     ESME_CHECK_ARG(ld_qkv % 8 == 0 && lo_qk % 8 == 0 && lo_qk > 0 && ld_o % 4 == 0 && ld_o >= (int64_t)H * d, "attn_qkpair: bad row strides / pair offset");
     ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0, "attn_qkpair: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && B <= 65535, "attn_qkpair: max_len must be > 0, H and B <= 65535");
+    ESME_CHECK_ARG(max_len > 0 && H <= 65535, "attn_qkpair: max_len must be > 0, H <= 65535");
     AttnSplitArgs sa{{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H, softmax_scale * 1.4426950408889634f, 1, H * B,
                       0.0f, 0, seq_order}, lo_qk, 0};
-    const dim3 grid((unsigned int)((max_len + QT - 1) / QT), (unsigned int)H, (unsigned int)B);
     const hipStream_t s = (hipStream_t)stream;
     // options variant 2, head dims 64 / 32: the key-axis-pipelined kernel (round 6; exact maxima: spec = 0, thr = 0).  Measured (profiles/r06_attn_sb_bench.txt):
     // 404 vs 363 us at 100 x 500, 636 vs 641 at 49 x 1 002, 1 140 vs 1 168 at 25 x 2 000 -- not the hoped-for 260 us, so the first-generation kernel stays the default
     const bool fits32 = ((int64_t)max_len + KT) * ld_qkv * 2 < 0xffffffffLL;
     if ((d == 64 || d == 32) && opts && opts->variant == 2 && ld_o % 8 == 0 && aligned16(o) && fits32)
         return d == 64 ? launch_sb<64, true, true, false>(sa, B, max_len, s) : launch_sb<32, true, true, false>(sa, B, max_len, s);
+    if (d != 16 && d != 32 && d != 64) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_qkpair: head dim must be 16, 32 or 64");
+    if (const int rc = generic_launch_ok(ld_qkv, max_len, QT, B, seq_order, "attn_qkpair")) return rc;
     switch (d) {
-        case 16: return launch_split<16, true, true>(sa, grid, s);
-        case 32: return launch_split<32, true, true>(sa, grid, s);
-        case 64: return launch_split<64, true, true>(sa, grid, s);
+        case 16: return launch_split<16, true, true>(sa, B, max_len, s);
+        case 32: return launch_split<32, true, true>(sa, B, max_len, s);
+        case 64: return launch_split<64, true, true>(sa, B, max_len, s);
         default: ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_qkpair: head dim must be 16, 32 or 64");
     }
 }

@@ -180,6 +180,11 @@ int esme_hip_qk_norm_rotary_f16_scaled(void* q, void* k, int64_t ld, const void*
  * rows only.  q, k, v: (T, H, d) views with row stride ld_qkv; o: (T, H*d) with row
  * stride ld_o.  bf16 operands, fp32 scores / softmax / accumulators, P rounded to bf16
  * before the PV product (flash-attention-2 convention).  d in {16, 32, 64, 128}.
+ * Limits (every attention entry point below): H <= 65 535; T < 2^31 (cu_lens is int32); any number of sequences B (the kernels that
+ * take the sequence from grid z run as several launches of at most 65 535 sequences).  The generic kernel (head dims 16 / 128,
+ * options variant 1, and the strides the software-pipelined kernels cannot address) and the split / q/k-pair kernels address rows inside
+ * one sequence with 32-bit element offsets: (max_len + rows) * ld_qkv must stay below 2^32 (rows = the kernel's query tile: 128, or
+ * 256 when max_len >= 192 in the generic kernel), else ESME_ERR_UNSUPPORTED.  seq_order with B > 65 535 on those kernels: ESME_ERR_ARG.
  * Replaces: flash_attn_varlen_func at esme/attention.py:115-123 (third-party CUDA). */
 int esme_hip_attn_varlen_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
                              void* o, int64_t ld_o, const int32_t* cu_lens, int B, int64_t T,
@@ -216,7 +221,8 @@ typedef struct esme_attn_opts {
                                   * the score accumulators start at -4.0, P = 2^(score - 4) stays inside fp16 for scores up to 20 (13.9 natural units);
                                   * a work item with a higher score, or with a row whose sum falls below S * 2^-14 (its P values average below fp16's smallest normal), is redone
                                   * with exact maxima: always correct, fast where a model's scores stay inside that window.  Variants 1 and 2, and a row stride for which
-                                  * (max_len + 64) rows do not fit 32-bit byte offsets, run the generic kernel with a unit scale instead (online softmax in log2 units) */
+                                  * (max_len + 64) rows pass 2^32 bytes, run the generic kernel with a unit scale instead (online softmax in log2 units; its own
+                                  * stride limit above) */
 } esme_attn_opts_t;
 int esme_hip_attn_varlen_fwd_opts(const void* q, const void* k, const void* v, int64_t ld_qkv,
                                   void* o, int64_t ld_o, const int32_t* cu_lens, int B, int64_t T,

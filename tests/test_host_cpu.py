@@ -177,6 +177,48 @@ def test_round6_entry_points_validate_without_gpu():
     assert b'q_prescaled' in lib.esme_hip_last_error()
 
 
+def test_attention_generic_kernel_limits_validate_without_gpu():
+    """The generic and split attention kernels address rows inside one sequence with 32-bit element offsets and take the sequence from
+    grid z (more than 65 535 sequences run as several launches that advance cu_lens).  Refused on the host, before any launch: a row stride
+    for which (max_len + the kernel's row tile) rows reach 2^32 elements, and a dispatch order with more than 65 535 sequences.  Every call
+    here is refused; that B = 70 000 is accepted is shown by tests/test_extreme_shapes_gpu.py."""
+    from esme import _hip
+    lib = _hip.load()
+    cu = 16
+    # (128 + 128 rows) * 2^24 = 2^32 elements: the first refused stride (max_len < 192: one 128-row q-block per wave)
+    ld = 1 << 24
+    for d, variant in ((16, 0), (128, 0), (64, 0), (32, 0), (64, 1), (64, 2)):        # head dims 64 / 32: fits32 fails, so the generic kernel
+        ao = _hip.AttnOpts(ctypes.sizeof(_hip.AttnOpts), variant, 0, 8.0, 1, None, 0, 0)
+        assert lib.esme_hip_attn_varlen_fwd_opts(16, 16, 16, ld, 16, 128, cu, 1, 8, 1, d, 128, 0.25, ctypes.byref(ao), None) == -2, (d, variant)
+        assert b'2^32' in lib.esme_hip_last_error()
+    assert lib.esme_hip_attn_varlen_fwd(16, 16, 16, ld, 16, 128, cu, 1, 8, 1, 16, 128, 0.25, None) == -2
+    assert lib.esme_hip_attn_varlen_fwd_exact(16, 16, 16, ld, 16, 128, cu, 1, 8, 1, 128, 128, 0.25, None) == -2
+    # max_len >= 192: two q-blocks per wave, a 256-row tile: (64 + 192) rows at 2^24 already reach 2^32
+    assert lib.esme_hip_attn_varlen_fwd(16, 16, 16, ld, 16, 128, cu, 1, 8, 1, 16, 192, 0.25, None) == -2
+    assert b'max_len + 256' in lib.esme_hip_last_error()
+    # the split ('exact') and q/k-pair ('half', robust) entries: 128-row tiles
+    for d in (16, 32, 64, 128):
+        assert lib.esme_hip_attn_varlen_fwd_split(16, 16, 16, ld, 64, 16, 512, 256, cu, 1, 8, 1, d, 128, 0.25, None, None) == -2, d
+        assert b'attn_split' in lib.esme_hip_last_error() and b'2^32' in lib.esme_hip_last_error()
+    for d in (16, 32, 64):
+        assert lib.esme_hip_attn_varlen_fwd_qkpair_f16(16, 16, 16, ld, 64, 16, 128, cu, 1, 8, 1, d, 128, 0.25, None, None) == -2, d
+        assert b'attn_qkpair' in lib.esme_hip_last_error() and b'2^32' in lib.esme_hip_last_error()
+    # a dispatch order with more than 65 535 sequences: the chunked launches advance cu_lens, an order into the whole batch would mis-index
+    B = 70000
+    for d, variant in ((16, 0), (128, 0), (64, 1), (32, 1)):
+        ao = _hip.AttnOpts(ctypes.sizeof(_hip.AttnOpts), variant, 0, 8.0, 1, 16, 0, 0)
+        assert lib.esme_hip_attn_varlen_fwd_opts(16, 16, 16, 128, 16, 128, cu, B, B, 1, d, 8, 0.25, ctypes.byref(ao), None) == -1, (d, variant)
+        assert b'seq_order' in lib.esme_hip_last_error()
+    for d in (16, 64):
+        assert lib.esme_hip_attn_varlen_fwd_split(16, 16, 16, 384, 192, 16, 128, 64, cu, B, B, 1, d, 8, 0.25, 16, None) == -1, d
+        assert b'seq_order' in lib.esme_hip_last_error()
+        assert lib.esme_hip_attn_varlen_fwd_qkpair_f16(16, 16, 16, 320, 192, 16, 64, cu, B, B, 1, d, 8, 0.25, 16, None) == -1, d
+        assert b'seq_order' in lib.esme_hip_last_error()
+    # the bounds that stay: H <= 65 535
+    assert lib.esme_hip_attn_varlen_fwd(16, 16, 16, 65536 * 16, 16, 65536 * 16, cu, 1, 8, 65536, 16, 8, 0.25, None) == -1
+    assert b'H <= 65535' in lib.esme_hip_last_error()
+
+
 def test_calibration_batch_covers_the_vocabulary_and_plan_keys():
     """precision 'half' (round 6), host side: the calibration batch holds every id of the alphabet except <pad> at least 8 times, cls / eos at the ends of
     its 8 sequences, is the same on every machine, and takes a caller's batch on board; HalfPlan keys derived weights on the channel LIST."""
