@@ -143,6 +143,12 @@ SIGNATURES = {
     'esme_hip_gather_rows': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'esme_hip_scatter_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     'esme_hip_segment_mean': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    'esme_hip_attn_pool_workspace_bytes': (c_int64, [c_int, c_int64, c_int, c_int, c_int]),
+    'esme_hip_attn_pool_fold': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'esme_hip_attn_pool': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_int64, c_int, c_void_p]),
+    'esme_hip_relu_linear': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
+                                     c_void_p]),
     'esme_hip_quantize_4bit': (c_int, [c_void_p, c_int64, c_int64, c_int, POINTER(c_float), c_void_p, c_void_p,
                                        c_void_p]),
     'esme_hip_dequantize_4bit': (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_float), c_void_p, c_void_p,
@@ -961,6 +967,74 @@ def segment_mean(x: torch.Tensor, cu_lens: torch.Tensor) -> torch.Tensor:
                                         out.data_ptr(), out.stride(0), 1 if x.dtype == torch.float32 else 0,
                                         _stream()), 'esme_hip_segment_mean')
     return out
+
+
+def attn_pool_fold(cls: torch.Tensor, w_k: torch.Tensor, heads: int) -> torch.Tensor:
+    """U (n_cls * heads, E) float32 = log2(e) / sqrt(d) * W_k[h d:(h+1) d, :]^T cls[c, h d:(h+1) d] (row c * heads + h): the key projection
+    folded into the class-token queries (esme_hip_attn_pool_fold).  cls (n_cls, E), w_k (E, E) bfloat16."""
+    cp, ldc = _rows2d(cls, 'attn_pool_fold cls')
+    wp, ldw = _rows2d(w_k, 'attn_pool_fold w_k')
+    n_cls, E = cls.shape
+    if tuple(w_k.shape) != (E, E):
+        raise ValueError(f'attn_pool_fold: w_k must be ({E}, {E}), got {tuple(w_k.shape)}')
+    U = torch.empty(n_cls * heads, E, dtype=torch.float32, device=cls.device)
+    with _Traced('attn_pool_fold', (n_cls, heads, E)):
+        _check(load().esme_hip_attn_pool_fold(cp, ldc, wp, ldw, E, int(heads), n_cls, U.data_ptr(), _stream()), 'esme_hip_attn_pool_fold')
+    return U
+
+
+def attn_pool_workspace_bytes(B: int, T: int, E: int, heads: int, n_cls: int) -> int:
+    n = load().esme_hip_attn_pool_workspace_bytes(int(B), int(T), int(E), int(heads), int(n_cls))
+    if n < 0:
+        _check(n, 'esme_hip_attn_pool_workspace_bytes')
+    return n
+
+
+def attn_pool(x: torch.Tensor, cu_lens: torch.Tensor, U: torch.Tensor, heads: int, n_cls: int) -> torch.Tensor:
+    """(B, n_cls, E) attention pooling of the packed rows of x (T, E), bfloat16 or float32, with the folded queries U of
+    attn_pool_fold (esme_hip_attn_pool); output in x's dtype.  cu_lens int32 (B+1) on the device (int64 is converted)."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'attn_pool: expected bfloat16 or float32 embeddings, got {x.dtype}')
+    xp, ldx = _rows2d(x, 'attn_pool x', x.dtype)
+    if cu_lens.dtype != torch.int32:
+        cu_lens = cu_lens.to(torch.int32)
+    cu_lens = cu_lens.contiguous()
+    T, E = x.shape
+    B = cu_lens.numel() - 1
+    if U.dtype != torch.float32 or tuple(U.shape) != (n_cls * heads, E) or not U.is_contiguous():
+        raise ValueError(f'attn_pool: U must be a contiguous float32 ({n_cls * heads}, {E}) tensor')
+    out = torch.empty(B, n_cls, E, dtype=x.dtype, device=x.device)
+    if B <= 0:
+        return out
+    ws = torch.empty(attn_pool_workspace_bytes(B, T, E, heads, n_cls), dtype=torch.uint8, device=x.device)
+    with _Traced('attn_pool', (B, T, E, heads, n_cls)):
+        _check(load().esme_hip_attn_pool(xp, ldx, _dev(cu_lens, 'cu_lens', torch.int32), B, T, E, int(heads), int(n_cls),
+                                         _dev(U, 'attn_pool U', torch.float32), ws.data_ptr(), ws.numel(), out.data_ptr(), n_cls * E,
+                                         1 if x.dtype == torch.float32 else 0, _stream()), 'esme_hip_attn_pool')
+    return out
+
+
+def relu_linear(h: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = relu(h) @ w.T + bias (esme_hip_relu_linear): h (M, K) bfloat16 or float32, w (N, K) bfloat16, bias (N) bfloat16 or None;
+    y (M, N) in h's dtype.  More than 64 outputs run in slices of 64."""
+    if h.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'relu_linear: expected bfloat16 or float32 input, got {h.dtype}')
+    hp, ldh = _rows2d(h, 'relu_linear h', h.dtype)
+    if not w.is_contiguous() or w.dim() != 2 or w.shape[1] != h.shape[1]:
+        raise ValueError(f'relu_linear: weight must be a contiguous (N, {h.shape[1]}) tensor')
+    M, K = h.shape
+    N = w.shape[0]
+    y = torch.empty(M, N, dtype=h.dtype, device=h.device)
+    wp = _dev(w, 'relu_linear w', torch.bfloat16)
+    bp = _dev(bias.contiguous(), 'relu_linear bias', torch.bfloat16) if bias is not None else None
+    es = y.element_size()
+    with _Traced('relu_linear', (M, N, K)):
+        for j0 in range(0, N, 64):
+            n = min(64, N - j0)
+            _check(load().esme_hip_relu_linear(hp, ldh, wp + j0 * K * 2, K, (bp + j0 * 2) if bp is not None else None,
+                                               y.data_ptr() + j0 * es, N, M, n, K, 1 if h.dtype == torch.float32 else 0, _stream()),
+                   'esme_hip_relu_linear')
+    return y
 
 
 def _codebook_arg(codebook):

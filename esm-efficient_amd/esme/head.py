@@ -1,7 +1,10 @@
-"""LM head on the HIP path (reference esme/head.py:8-27: dense -> GELU -> LN -> vocab).
+"""Heads on the HIP path: the LM head (reference esme/head.py:8-27: dense -> GELU -> LN -> vocab)
+and the mean-pooling classification head `ClsHead` (esme/head.py:30-68).
 
 The exact-erf GELU is the dense GEMM's epilogue; the vocab projection (N = 33 / 64,
-HBM-bound) runs on the same GEMM kernel with row-clamped weight loads."""
+HBM-bound) runs on the same GEMM kernel with row-clamped weight loads.  ClsHead pools
+with esme_hip_segment_mean, runs its first Linear on the GEMM and the ReLU + last Linear
+in esme_hip_relu_linear (inference only)."""
 from __future__ import annotations
 
 import torch
@@ -9,6 +12,7 @@ from torch import nn
 
 from esme import _hip
 from esme.nn import LayerNorm, Linear
+from esme.pooling import PartitionMeanPool, _ReluMLP
 
 
 class RobertaLMHead(nn.Module):
@@ -67,3 +71,27 @@ class RobertaLMHead(nn.Module):
             self.layer_norm(h[:, :E], out=h[:, :E])
             y = _hip.gemm(h, fw, self.final.bias)
         return y.view(*shape[:-1], y.shape[-1])
+
+
+class ClsHead(nn.Module):
+    """head(mean pool of each sequence's rows).squeeze(-1) (reference esme/head.py:30-68): `forward(x, cu_lens)` -> (n_seq, num_cls),
+    or (n_seq,) for one class.  Keys `head.0.*`, `head.2.*`; x bfloat16 or float32 (the output keeps its dtype).  Parameters are
+    bfloat16 whatever `dtype` says; fp32 checkpoints cast on load_state_dict."""
+
+    def __init__(self, embed_dim, num_cls=1, hidden_dim=4096, dtype=torch.bfloat16):
+        super().__init__()
+        if embed_dim % 8 != 0 or hidden_dim % 8 != 0:
+            raise ValueError('ClsHead: embed_dim and hidden_dim must be multiples of 8')
+        self.pool = PartitionMeanPool()
+        self.head = nn.Sequential(
+            Linear(embed_dim, hidden_dim, dtype=torch.bfloat16),
+            nn.ReLU(),                                 # slot only: the ReLU runs inside esme_hip_relu_linear
+            Linear(hidden_dim, num_cls, dtype=torch.bfloat16),
+        )
+        self._mlp = _ReluMLP()
+
+    def forward(self, x, cu_lens):
+        if x.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f'ClsHead: x must be bfloat16 or float32, got {x.dtype}')
+        pooled = self.pool(x, cu_lens)
+        return self._mlp(pooled, self.head[0], self.head[2]).squeeze(-1)

@@ -497,6 +497,37 @@ int esme_hip_scatter_rows(const void* src, const int64_t* idx, void* dst, int64_
 int esme_hip_segment_mean(const void* x, int64_t ldx, const int32_t* cu_lens, int B, int E,
                           void* out, int64_t ldo, int dtype_f32, void* stream);
 
+/* Attention pooling (reference esme/pooling.py:72-228: AttentionPool ... BinaryLearnedAggregation, its second
+ * flash_attn_varlen_func call site), in three launches with the key projection folded into the queries:
+ *   out[s, c, h d + i] = sum_{t in s} softmax_t(u_{c,h} . x_t / sqrt(d)) x_t[h d + i],  u_{c,h} = W_k[h d:(h+1) d, :]^T cls[c, h d:(h+1) d],
+ * d = E / heads.  The reference's k bias adds cls . b_k, a constant over t, to every score of a (c, h): it cancels in the softmax, so
+ * it is no operand here (there it moves the result only through the bf16 rounding of k).
+ *
+ * esme_hip_attn_pool_fold: U (n_cls * heads, E) fp32, contiguous, 16-byte aligned <- log2(e) / sqrt(d) * u_{c,h} in row c * heads + h
+ * (fp32 fmaf chain over the d products, then the scale).  cls: bf16 (n_cls, E) row stride ldc; w_k: bf16 (E, E) row stride ldw.  Run it on
+ * every call: it is n_cls E^2 MACs, and a cached U could go stale after an in-place weight edit.
+ * esme_hip_attn_pool: out (B, n_cls * E), row stride ldo >= n_cls * E, in x's dtype (bf16: dtype_f32 = 0; fp32: 1), rounded once.
+ * x: (T, E) row stride ldx (a multiple of 8 for bf16 / 4 for fp32), 16-byte aligned; cu_lens int32 (B+1) on the device with
+ * cu_lens[B] <= T (never read on the host).  Work items are chunks of 64 rows that start at each sequence's first row; a second
+ * launch merges a sequence's chunks in chunk order, so the result is deterministic and a sequence's output does not depend on the
+ * other sequences of the batch.  A zero-length sequence pools to zeros.
+ * workspace: esme_hip_attn_pool_workspace_bytes(B, T, E, heads, n_cls) bytes, 16-byte aligned, no initialisation needed:
+ * (B + floor(T / 64) + 1) * (2 n_cls heads + n_cls E) * 4 bytes.
+ * Limits: E % heads == 0 and E % 8 == 0 (else ESME_ERR_ARG); n_cls * heads <= 512 (else ESME_ERR_UNSUPPORTED); any head dim d.
+ * The workspace query returns the same negative codes for a bad geometry. */
+int64_t esme_hip_attn_pool_workspace_bytes(int B, int64_t T, int E, int heads, int n_cls);
+int esme_hip_attn_pool_fold(const void* cls, int64_t ldc, const void* w_k, int64_t ldw, int E, int heads, int n_cls,
+                            float* U, void* stream);
+int esme_hip_attn_pool(const void* x, int64_t ldx, const int32_t* cu_lens, int B, int64_t T, int E, int heads, int n_cls,
+                       const float* U, void* workspace, int64_t ws_bytes, void* out, int64_t ldo, int dtype_f32, void* stream);
+
+/* y[r, j] = b[j] + sum_k W[j, k] relu(h[r, k]), j < N <= 64 (else ESME_ERR_UNSUPPORTED): the last Linear of the pooling heads after
+ * their ReLU (esme/pooling.py:210-211 final(relu(linear(x))), esme/head.py:59-63).  h: (M, K) bf16 (dtype_f32 = 0) or fp32 (1), row
+ * stride ldh; W: bf16 (N, K) row stride ldw (a multiple of 8); bias: bf16 (N) or NULL; y: (M, N) in h's dtype, row stride ldy.
+ * K % 8 == 0, 16-byte aligned h and W rows.  fp32 accumulation, one rounding. */
+int esme_hip_relu_linear(const void* h, int64_t ldh, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
+                         int64_t M, int N, int K, int dtype_f32, void* stream);
+
 /* ---- 4-bit weight-only block quantisation ("esme-q4") ------------------------------
  * The reference delegates this to bitsandbytes.nn.Linear4bit (esme/esm.py:434-446,
  * :482-484, :915-946), a third-party CUDA library that is not vendored; the format here is
