@@ -149,6 +149,9 @@ SIGNATURES = {
                                    c_void_p, c_int64, c_int, c_void_p]),
     'esme_hip_relu_linear': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
                                      c_void_p]),
+    'esme_hip_lora_down': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    'esme_hip_lora_down_ln': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int64,
+                                      c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'esme_hip_quantize_4bit': (c_int, [c_void_p, c_int64, c_int64, c_int, POINTER(c_float), c_void_p, c_void_p,
                                        c_void_p]),
     'esme_hip_dequantize_4bit': (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_float), c_void_p, c_void_p,
@@ -1035,6 +1038,33 @@ def relu_linear(h: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
                                                y.data_ptr() + j0 * es, N, M, n, K, 1 if h.dtype == torch.float32 else 0, _stream()),
                    'esme_hip_relu_linear')
     return y
+
+
+def lora_down(x: torch.Tensor, A: torch.Tensor, u: torch.Tensor, ln=None) -> torch.Tensor:
+    """u (T, X) = x (T, E) @ A (rank, E).T, bfloat16, columns rank .. X-1 zero: the down-projection of the LoRA adapters of one GEMM,
+    written into that GEMM's extension K-tile (esme_hip_lora_down; `u` is usually the column block E .. E+X-1 of the buffer that
+    holds x).  `ln` = (partial (nblk, T, 2) f32 sums, dim, eps, c1 (rank,) f32, bA (rank,) f32): the form for a LayerNorm-folded GEMM
+    (esme_hip_lora_down_ln; A is then the gamma-scaled matrix)."""
+    xp, ldx = _rows2d(x, 'lora_down x')
+    up, ldu = _rows2d(u, 'lora_down u')
+    if A.dim() != 2 or not A.is_contiguous() or A.shape[1] != x.shape[1]:
+        raise ValueError(f'lora_down: A must be a contiguous (rank, {x.shape[1]}) tensor')
+    T, E = x.shape
+    R, X = A.shape[0], u.shape[1]
+    if u.shape[0] != T:
+        raise ValueError('lora_down: u must have as many rows as x')
+    ap = _dev(A, 'lora_down A', torch.bfloat16)
+    with _Traced('lora_down', (T, X, E, ln is not None)):
+        if ln is None:
+            _check(load().esme_hip_lora_down(xp, ldx, ap, R, T, E, X, up, ldu, _stream()), 'esme_hip_lora_down')
+        else:
+            part, dim, eps, c1, bA = ln
+            if part.dim() != 3 or part.shape[1] != T or part.shape[2] != 2 or not part.is_contiguous() or c1.numel() != R or bA.numel() != R:
+                raise ValueError('lora_down: LayerNorm tensors have the wrong shape')
+            _check(load().esme_hip_lora_down_ln(xp, ldx, ap, R, T, E, X, up, ldu, _dev(part, 'ln partial', torch.float32), part.shape[0],
+                                                int(dim), float(eps), _dev(c1, 'lora c1', torch.float32), _dev(bA, 'lora bA', torch.float32),
+                                                _stream()), 'esme_hip_lora_down_ln')
+    return u
 
 
 def _codebook_arg(codebook):

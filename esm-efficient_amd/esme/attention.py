@@ -48,7 +48,7 @@ def _q_scale(head_dim: int) -> float:
 class ForwardContext:
     """Per-forward shared state: row positions, rotary tables (computed once, not per
     layer) and the LayerNorm-statistics plumbing of the fused path."""
-    __slots__ = ('pos', 'cos', 'sin', 'sums', 'part_a', 'part_b', 'fold', 'exact_attn', 'x32', 'order', 'scratch', 'f16', 'xs', 'plan', 'probe', 'ovf', 'cos32', 'sin32', 'guard')
+    __slots__ = ('pos', 'cos', 'sin', 'sums', 'part_a', 'part_b', 'fold', 'exact_attn', 'x32', 'order', 'scratch', 'f16', 'xs', 'plan', 'probe', 'ovf', 'cos32', 'sin32', 'guard', 'lora_x')
 
     def __init__(self, pos, cos, sin, fold=False, exact_attn=False, f16=False, plan=None):
         self.pos, self.cos, self.sin = pos, cos, sin
@@ -67,6 +67,7 @@ class ForwardContext:
         self.sums = None            # partial sums (nblk, T, 2) f32 describing the current residual stream
         self.part_a = None          # (stats_blocks, T, 2) f32 buffers the residual GEMMs write their row sums to
         self.part_b = None
+        self.lora_x = None          # LoRA: the (T, E + X) buffer whose first E columns ARE the residual stream; the last X hold the QKV adapters' down-projection
 
 
 SUPPORTED_HEAD_DIMS = (16, 32, 64, 128)        # head dims of the attention / fused-rotary kernels
@@ -302,6 +303,8 @@ class FlashMultiheadAttention(nn.Module):
         self._q4_qkv = None         # esme.quantization.Q4Matrix pair when the layer is 4-bit
         self._q4_out = None
         self._out_w = self._out_b = None    # padded out-projection (padded layouts only)
+        self._has_lora = False      # set by ESM2.add_lora: q / k / v / out may be esme.lora.LoRA wrappers
+        self._lora_cache = None     # (key, derived adapter weights): _lora_weights
 
     # -- weight layout ------------------------------------------------------
     def _pack(self):
@@ -421,9 +424,10 @@ class FlashMultiheadAttention(nn.Module):
     def _qkv(self, x, lora_names=None):
         """LN -> fused QKV (-> ESM-C q/k LayerNorm over the full E, attention.py:104-105).
         Returns q, k, v as (T, H, d) views of one (T, 3E) buffer."""
-        assert lora_names is None, 'LoRA adapters are outside the inference hot path'
         if self.padded:
             raise NotImplementedError('the unfused stage methods are not available for padded layouts')
+        if self._has_lora:                                  # adapters (None / empty `lora_names`: all of them)
+            return self._split_qkv(self._qkv_lora_unfused(x, self._lora_weights(lora_names, False), None))
         w, b, _, _ = self._weights_qkv(False)
         qkv = _hip.gemm(self.norm(x), w, b)
         return self._split_qkv(qkv)
@@ -436,7 +440,7 @@ class FlashMultiheadAttention(nn.Module):
         H, d = self.num_heads, self.head_pad
         return tuple(qkv[:, i * E:(i + 1) * E].view(T, H, d) for i in range(3))
 
-    def _attn(self, q, k, v, cu_lens, max_len, exact=False, order=None, q_prescaled=False):
+    def _attn(self, q, k, v, cu_lens, max_len, exact=False, order=None, q_prescaled=False, out=None):
         """(T, H, d) x 3 -> (T, E), the reference's `_attn` (esme/attention.py:112-124).  The kernel reads q, k, v with ONE
         row stride (the layer hands it column blocks of the fused (T, 3E) projection); a caller that passes separately
         allocated tensors, as the reference's call sites may, gets them repacked."""
@@ -445,7 +449,7 @@ class FlashMultiheadAttention(nn.Module):
         if not (q.stride(0) == k.stride(0) == v.stride(0)) or q.stride(-1) != 1 or k.stride(-1) != 1 or v.stride(-1) != 1:
             q, k, v = (t.reshape(T, E).contiguous() for t in (q, k, v))
         return _hip.attn_varlen(q.view(T, E), k.view(T, E), v.view(T, E), cu_lens, max_len, self.num_heads,
-                                softmax_scale=self.head_dim ** -0.5, exact=exact, order=order, q_prescaled=q_prescaled)
+                                softmax_scale=self.head_dim ** -0.5, exact=exact, order=order, q_prescaled=q_prescaled, out=out)
 
     def forward(self, x, cu_lens, max_len, lora_names=None, ctx: Optional[ForwardContext] = None,
                 resid=None, alpha: float = 1.0, out=None, x_stats=None, stats_out=None, resid32=None, resid_pair=None, pair_scale=None,
@@ -454,8 +458,11 @@ class FlashMultiheadAttention(nn.Module):
         resid + alpha * (attn @ W_o^T + b_o) (written to `out`, which may alias resid).
         `x_stats` ((nblk, T, 2) f32 partial row sums of x) selects the LN-folded projection;
         `stats_out` makes the out-projection emit the statistics of its output.  `resid32` (high-precision mode): the fp32
-        residual stream, updated in place by the out-projection's epilogue; `out` receives its bf16 rounding."""
-        assert lora_names is None, 'LoRA adapters are outside the inference hot path'
+        residual stream, updated in place by the out-projection's epilogue; `out` receives its bf16 rounding.
+        `lora_names`: on a block with LoRA adapters (ESM2.add_lora), the adapters to apply (None / empty: all of them)."""
+        if self._has_lora:
+            return self._forward_lora(x, cu_lens, max_len, lora_names, ctx, resid, alpha, out, x_stats, stats_out,
+                                      resid32 is not None or resid_pair is not None)
         T = x.shape[0]
         E = self.attn_dim                                   # width of each of q, k, v (H * padded head dim)
         H, d = self.num_heads, self.head_pad
@@ -519,6 +526,137 @@ class FlashMultiheadAttention(nn.Module):
         if resid is not None or resid32 is not None or resid_pair is not None:
             return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out, resid32=resid32, resid_pair=resid_pair,
                                    pair_scale=pair_scale, pair_ext=pair_ext, col_absmax=g_col if resid_pair is not None else None)
+        return _hip.gemm(a, wo, bo, out=out)
+
+    # -- LoRA adapters (esme/lora.py): the delta rides in an extension K-tile of the projection's own GEMM --------------------
+    def _lora_weights(self, lora_names, fold: bool):
+        """Derived weights of the adapters `lora_names` selects (None / empty: all), cached on the parameters' version counters and the
+        selection:  {'qkv': (X, A, c1A, bA, [W | s B | 0]) or None, 'out': (X, A, [W_o | s B | 0]) or None}.  The A matrices of all selected
+        adapters of q, k and v are stacked to one (R, E) operand of esme_hip_lora_down; s B of each sits in the rows of its own
+        projection, zero elsewhere.  `fold`: for the LayerNorm-folded QKV GEMM, whose epilogue multiplies the accumulator by rstd -- A
+        carries gamma (A' = bf16(gamma * A)), c1A = rowsum(A'), bA = A beta, and the kernel writes LN(x) A^T / rstd."""
+        from esme.lora import LoRA, ext_width
+        if self.padded:
+            raise NotImplementedError('LoRA adapters are not implemented for padded layouts (head dim 24 / a width that is not a multiple of 64)')
+        if self._q4_qkv is not None or self._q4_out is not None:
+            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters)')
+        mods = {p: getattr(self, p) for p in ('q', 'k', 'v', 'out') if isinstance(getattr(self, p), LoRA)}
+        sel = {p: m.select(lora_names) for p, m in mods.items()}
+        params = [t for p, m in mods.items() for t in m.params(sel[p])]
+        if fold:
+            self._pack_fold()
+        else:
+            self._pack()
+        key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), self._fold_key if fold else self._pack_key,
+               _version_key(self.out.weight, *params))
+        if self._lora_cache is not None and self._lora_cache[0] == key:
+            return self._lora_cache[1]
+        E = self.embed_dim
+        res = {'qkv': None, 'out': None}
+        with torch.no_grad():
+            blocks = [(i, *mods[p].stacked(sel[p])) for i, p in enumerate(('q', 'k', 'v')) if p in mods]
+            if blocks:
+                A = torch.cat([b[1] for b in blocks], dim=0).contiguous()
+                X = ext_width(A.shape[0])
+                c1A = bA = None
+                base = self._qkv_w
+                if fold:
+                    base = self._fold[0]
+                    Af = A.float()
+                    A = (Af * self.norm.weight.data.float().unsqueeze(0)).to(torch.bfloat16).contiguous()
+                    c1A = A.float().sum(dim=1).contiguous()
+                    bA = (Af @ self.norm.bias.data.float()).contiguous() if self.norm.bias is not None else torch.zeros_like(c1A)
+                we = torch.zeros(3 * E, E + X, dtype=torch.bfloat16, device=base.device)
+                we[:, :E] = base
+                o = E
+                for i, a, b in blocks:
+                    we[i * E:(i + 1) * E, o:o + a.shape[0]] = b.to(torch.bfloat16)
+                    o += a.shape[0]
+                res['qkv'] = (X, A, c1A, bA, we)
+            if 'out' in mods:
+                A, B = mods['out'].stacked(sel['out'])
+                X = ext_width(A.shape[0])
+                wo = self.out.weight.data
+                we = torch.zeros(E, E + X, dtype=torch.bfloat16, device=wo.device)
+                we[:, :E] = wo
+                we[:, E:E + B.shape[1]] = B.to(torch.bfloat16)
+                res['out'] = (X, A.contiguous(), we)
+        self._lora_cache = (key, res)
+        return res
+
+    def lora_ext_widths(self, lora_names):
+        """(X of the QKV GEMM, X of the out-projection) for this selection (0: that GEMM has no adapter)."""
+        lw = self._lora_weights(lora_names, True)
+        return (lw['qkv'][0] if lw['qkv'] else 0, lw['out'][0] if lw['out'] else 0)
+
+    def _qkv_lora_unfused(self, x, lw, rot):
+        """LayerNorm kernel -> [h | h A^T] -> plain QKV GEMM over [W | s B] (the stage form, and the path without LayerNorm fold)."""
+        w, b, _, _ = self._weights_qkv(False)
+        if lw['qkv'] is None:
+            return _hip.gemm_fused(self.norm(x), w, b, rot=rot)
+        X, A, _, _, we = lw['qkv']
+        E = self.embed_dim
+        he = torch.empty(x.shape[0], E + X, dtype=torch.bfloat16, device=x.device)
+        self.norm(x, out=he[:, :E])
+        _hip.lora_down(he[:, :E], A, he[:, E:])
+        return _hip.gemm_fused(he, we, b, rot=rot)
+
+    def _forward_lora(self, x, cu_lens, max_len, lora_names, ctx, resid, alpha, out, x_stats, stats_out, high):
+        """The attention branch of precision 'fast' with adapters: the launches of `forward` plus one esme_hip_lora_down in front of each GEMM
+        that has adapters; that GEMM then runs over K = E + X.  With every lora_B zero the extension adds exact zeros to the fp32
+        accumulators, so the result equals the block's without adapters bit for bit."""
+        if self.training:
+            raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
+        if high or (ctx is not None and (ctx.f16 or ctx.exact_attn)):
+            raise NotImplementedError("LoRA adapters run in precision 'fast' only ('high', 'half' and 'exact' have no adapter path)")
+        T = x.shape[0]
+        E = self.attn_dim
+        H, d = self.num_heads, self.head_pad
+        fold = x_stats is not None
+        lw = self._lora_weights(lora_names, fold)
+        rot_fusable = (self.rot_emb is not None and ctx is not None and not self.pre_layernorm and d in (16, 32, 64) and E % 32 == 0)
+        rot = (ctx.cos, ctx.sin, ctx.pos, d, 2 * E) if rot_fusable else None
+        qk_pass = (self.pre_layernorm and self.rot_emb is not None and ctx is not None and d in (16, 32, 64, 128) and E <= 5120)
+        qp = bool(_ATTN_QP and (rot_fusable or qk_pass) and d in (32, 64) and E % 64 == 0 and fold)
+        if not fold:
+            qkv = self._qkv_lora_unfused(x, lw, rot)
+        else:
+            wf, _, c1, c2 = self._weights_qkv(True)
+            a_op = x
+            if lw['qkv'] is not None:
+                X, A, c1A, bA, wf = lw['qkv']
+                xe = ctx.lora_x if ctx is not None else None
+                if xe is None or xe.data_ptr() != x.data_ptr() or xe.stride(0) != x.stride(0) or xe.shape[1] < E + X:
+                    xe = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)       # (a caller outside the model's forward: x moves once)
+                    xe[:, :E].copy_(x)
+                _hip.lora_down(xe[:, :E], A, xe[:, E:E + X], ln=(x_stats, self.embed_dim, self.norm.eps, c1A, bA))
+                a_op = xe[:, :E + X]
+            qkv = _hip.gemm_fused(a_op, wf, None, ln=(x_stats, self.embed_dim, self.norm.eps, c1, c2, None), rot=rot,
+                                  q_scale=_q_scale(self.head_dim) if (qp and rot_fusable) else 0.0)
+        if qk_pass:
+            _hip.qk_norm_rotary_(qkv[:, :E], qkv[:, E:2 * E], self.layernorm_q.weight, self.layernorm_k.weight,
+                                 self.layernorm_q.bias, self.layernorm_k.bias, self.layernorm_q.eps,
+                                 ctx.cos, ctx.sin, ctx.pos, H, q_scale=_q_scale(self.head_dim) if qp else 1.0)
+            q, k, v = (qkv[:, i * E:(i + 1) * E].view(T, H, d) for i in range(3))
+        else:
+            q, k, v = self._split_qkv(qkv)
+            if self.rot_emb is not None and rot is None:
+                if ctx is not None:
+                    _hip.rotary_(q.view(T, E), k.view(T, E), ctx.cos, ctx.sin, ctx.pos, H)
+                else:
+                    q, k = self.rot_emb(q, k, cu_lens, max_len, inplace=True)
+        order = ctx.order if ctx is not None else None
+        if lw['out'] is None:
+            a = self._attn(q, k, v, cu_lens, max_len, order=order, q_prescaled=qp)
+            wo, bo = self._weights_out()
+        else:
+            X, A, wo = lw['out']
+            bo = self.out.bias
+            a = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)
+            self._attn(q, k, v, cu_lens, max_len, order=order, q_prescaled=qp, out=a[:, :E])
+            _hip.lora_down(a[:, :E], A, a[:, E:])
+        if resid is not None:
+            return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out)
         return _hip.gemm(a, wo, bo, out=out)
 
 

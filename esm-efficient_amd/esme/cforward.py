@@ -145,6 +145,8 @@ class ModelDescriptor:
     def supported(model, precision: str = 'fast') -> bool:
         if not len(model.layers) or model.precision != precision or model.phys_dim % 64:
             return False
+        if getattr(model, 'has_lora', False):       # LoRA adapters run on the module path (esme.attention._forward_lora); the descriptor has no slot for them
+            return False
         if precision == 'exact':                    # nothing is folded in this mode; the split-operand kernels cover head dims 16 / 32 / 64 / 128
             att = model.layers[0].self_attn
             return att.head_pad in (16, 32, 64, 128) and not any(q is not None for layer in model.layers for q in
@@ -176,8 +178,15 @@ def _workspace(model, key, nbytes, device):
     return ws
 
 
+def _refuse_lora(model):
+    """The one-call C forward would run WITHOUT the adapters of a model that has some: refuse."""
+    if getattr(model, 'has_lora', False):
+        raise NotImplementedError('the one-call C forward (esme_hip_forward*) has no LoRA adapter path: a model with adapters runs module by module')
+
+
 def forward_layers(model, x, cu_lens, max_len, pos, cos, sin):
     """In place on x (T, phys_dim): all layers + final LayerNorm through ONE C call."""
+    _refuse_lora(model)
     lib = _bind()
     md = getattr(model, '_cdesc', None)
     if md is None or md.key != ModelDescriptor.signature(model):
@@ -201,6 +210,7 @@ def forward_layers_half(model, x32, cu_lens, max_len, pos, cos, sin, pair, rep32
     """precision 'half': fp32 stream at the start `x32` (T, phys_dim) -> all layers + final LayerNorm through ONE C call
     (esme_hip_forward_half); fills `pair` (T, 2 * phys_dim) bf16 = [hi | lo] of the final LayerNorm and `rep32` (T, phys_dim) fp32.
     `plan`: the model's HalfPlan (cos / sin are float32 tables when it asks for q / k pairs)."""
+    _refuse_lora(model)
     lib = _bind()
     md = getattr(model, '_cdesc16', None)
     if md is None or md.key != ModelDescriptor.signature(model) or md.plan is not plan:
@@ -227,6 +237,7 @@ def forward_layers_exact(model, x32, cu_lens, max_len, pos, cos, sin, pair, rep3
     """precision 'exact': fp32 stream `x32` (T, phys_dim), updated in place -> all layers + final LayerNorm through ONE C call
     (esme_hip_forward_exact); fills `pair` (T, 2 * phys_dim) bf16 = [hi | lo] of the final LayerNorm and `rep32` (T, phys_dim) fp32.
     cos / sin: FLOAT32 tables."""
+    _refuse_lora(model)
     lib = _bind()
     md = getattr(model, '_cdesc_exact', None)
     if md is None or md.key != ModelDescriptor.signature(model):

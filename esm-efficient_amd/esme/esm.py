@@ -11,7 +11,8 @@ that is not on a HIP device raises (there is no CPU fallback).
 
 `quantization='4bit'` / `'8bit'` keep the layer projections 4-bit / int8 in HBM (esme/quantization.py).
 ESM-1b / ESM-1v (learned positions, no rotary) run on the same kernels (`ESM1b`, `ESM1v`).
-Out of scope here: LoRA management, int8-activation matmuls,
+LoRA adapters (`add_lora` / `load_lora` / `save_lora`, `lora_names=`) run for inference in precision 'fast' (esme/lora.py).
+Out of scope here: training (no backward), int8-activation matmuls,
 activation checkpointing (training only), hub download (no network).
 """
 from __future__ import annotations
@@ -199,6 +200,8 @@ class ESM2(nn.Module):
         OWN data, packed like a forward's input -- calibrated on in addition to the built-in whole-vocabulary batch (the plan is then decided
         on what the model will really see; the run-time guard covers the rest)."""
         assert mode in ('fast', 'high', 'half', 'exact'), mode
+        if mode != 'fast' and self.has_lora:
+            raise NotImplementedError(f"precision {mode!r} has no LoRA adapter path: adapters run in precision 'fast' only")
         from esme.attention import HalfPlan
         changed = mode != self.precision
         self.precision = mode
@@ -566,21 +569,22 @@ class ESM2(nn.Module):
                                lora_names=None, layers=None):
         """Per-token representations: (T, E) for packed input, (B, S, E) when padded;
         with `layers=[...]` the raw outputs of those layers are concatenated after the
-        final-LayerNorm output on the feature axis (esm.py:201-266)."""
-        assert lora_names is None, 'LoRA adapters are outside the inference hot path'
+        final-LayerNorm output on the feature axis (esm.py:201-266).  `lora_names`: the adapters to apply on a model that has
+        some (None / empty: all of them; an unknown name raises KeyError)."""
         layers = list(layers) if layers else []
         self._check_layers_arg(layers)
 
         with _hip.stream_scope(self.embed_tokens.weight.device):
-            x = self._forward_representation(tokens, pad_args, pad_output, pad_indices, layers)
+            x = self._forward_representation(tokens, pad_args, pad_output, pad_indices, layers, lora_names=lora_names)
             if self.padded:                                       # physical -> logical width, per concatenated block
                 E, Ep = self.embed_dim, self.phys_dim
                 x = torch.cat([x[..., i * Ep:i * Ep + E] for i in range(x.shape[-1] // Ep)], dim=-1)
             return x
 
-    def _forward_representation(self, tokens, pad_args, pad_output, pad_indices, layers, want_pair=False):
+    def _forward_representation(self, tokens, pad_args, pad_output, pad_indices, layers, want_pair=False, lora_names=None):
         """forward_representation at the PHYSICAL width (== the logical one unless the layout is padded).  `want_pair`
         (precision 'exact' only): return the (hi, lo) bf16 pair of the final-LayerNorm output, the LM head's operand."""
+        lora = self._lora_select(lora_names)                   # None without adapters; else the names this call applies
         x = self._embedding_phys(tokens, pad_args)
         if pad_args is not None:
             assert tokens.ndim == 1, 'tokens are expected to be unpadded with shape (batch * seq_len)'
@@ -686,11 +690,18 @@ class ESM2(nn.Module):
             cforward.forward_layers(self, x, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin)
         else:
             ctx.order = _hip.seq_order(cu_lens)     # longest sequences' attention work first (speed only; the C entry does the same)
+            if lora is not None:
+                x = self._lora_stream(x, lora, ctx)
             for i, layer in enumerate(self.layers):
-                x = layer(x, cu_lens, max_len, None, ctx, inplace=True)
+                x = layer(x, cu_lens, max_len, lora, ctx, inplace=True)
                 if i in layers:
-                    taps.append(x.clone())
-            self.emb_layer_norm_after(x[:, :E], out=x[:, :E])        # pad columns (if any) stay zero
+                    taps.append(x.clone(memory_format=torch.contiguous_format) if lora is not None else x.clone())
+            if ctx.lora_x is not None:                                # the stream lives inside the wide buffer: the final LayerNorm moves it out
+                y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+                self.emb_layer_norm_after(x, out=y)
+                x = y
+            else:
+                self.emb_layer_norm_after(x[:, :E], out=x[:, :E])        # pad columns (if any) stay zero
 
         return self._finish_representation(x, taps, pad_output, pad_args, pad_indices, cu_lens, pad_width)
 
@@ -703,13 +714,12 @@ class ESM2(nn.Module):
 
     def forward(self, tokens, pad_args=None, pad_output=False, pad_indices=None, lora_names=None):
         """Logits (T, V) / (B, S, V), bf16 (fp32 with precision 'exact' / 'half'), on the model's device (esm.py:268-282)."""
-        assert lora_names is None, 'LoRA adapters are outside the inference hot path'
         with _hip.stream_scope(self.embed_tokens.weight.device):
             if self.precision in ('exact', 'half'):           # fp32 logits from the (hi, lo) pair of the final LayerNorm
-                pair = self._forward_representation(tokens, pad_args, pad_output, pad_indices, [], want_pair=True)
+                pair = self._forward_representation(tokens, pad_args, pad_output, pad_indices, [], want_pair=True, lora_names=lora_names)
                 y = self.lm_head.forward_exact(pair.reshape(-1, pair.shape[-1]))
                 return y.view(*pair.shape[:-1], y.shape[-1])
-            return self.lm_head(self._forward_representation(tokens, pad_args, pad_output, pad_indices, []))
+            return self.lm_head(self._forward_representation(tokens, pad_args, pad_output, pad_indices, [], lora_names=lora_names))
 
     def _checked(self, run, tokens=None):
         """Run `run()` (a forward ending in a softmax) and, in precision 'half' with half_check = 'sync', look at the range flag and the plan
@@ -745,6 +755,9 @@ class ESM2(nn.Module):
         the same shape overwrites.  'predict_log_prob' in precision 'half' with half_check = 'sync' checks the token ids, the range flag and the
         plan after each replay, as the eager call does (a widened plan is re-captured and replayed once)."""
         assert what in ('forward', 'forward_representation', 'predict_log_prob')
+        if self.has_lora:
+            raise NotImplementedError('graphed(): hipGraph replay is not implemented for a model with LoRA adapters (a graph bakes one adapter '
+                                      'selection and its derived weights in); call the model directly')
         if getattr(self, '_graph_cache', None) is None:
             from esme.graph import GraphCache
             self._graph_cache = GraphCache(self)
@@ -778,6 +791,130 @@ class ESM2(nn.Module):
         self.__dict__.pop('_cws', None)
         from esme.nn import bump_epoch
         bump_epoch()
+
+    # -- LoRA adapters (inference; esme/lora.py) ---------------------------------------------------------------------
+    _LORA_TARGETS = (('query', 'q'), ('key', 'k'), ('value', 'v'), ('output', 'out'))
+
+    @property
+    def has_lora(self) -> bool:
+        return bool(self.__dict__.get('_lora_attached', False))
+
+    def _lora_select(self, lora_names):
+        """None on a model without adapters (`lora_names` is then ignored, as in the reference); else the tuple of adapter names this call
+        applies -- all of them for None / an empty list.  KeyError for an unknown name; NotImplementedError where the adapters could not
+        be applied (any precision but 'fast', train mode): a forward never runs silently without them."""
+        if not self.has_lora:
+            return None
+        if self.precision != 'fast':
+            raise NotImplementedError(f"precision {self.precision!r} has no LoRA adapter path: adapters run in precision 'fast' only")
+        if self.training:
+            raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
+        have = self.lora_names()
+        if not lora_names:
+            return tuple(have)
+        for n in lora_names:
+            if n not in have:
+                raise KeyError(f'LoRA adapter {n!r} not found (available: {have})')
+        return tuple(lora_names)
+
+    def lora_names(self) -> list:
+        """Names of the attached adapters, in the order they were added."""
+        from esme.lora import lora_modules
+        mods = lora_modules(self)
+        return list(mods[0].lora_A.keys()) if mods else []
+
+    def _lora_stream(self, x, lora, ctx):
+        """The residual stream moved into the first E columns of a (T, E + X) buffer (X: the extension K-tile of the QKV GEMM for this
+        adapter selection): every layer's esme_hip_lora_down writes next to the stream, and the LayerNorm-folded QKV GEMM reads [x | u]
+        as ONE operand.  Returns the stream as a view of that buffer (x itself when q, k and v carry no adapter)."""
+        X = self.layers[0].self_attn.lora_ext_widths(lora)[0]
+        if not X or not ctx.fold or x.shape[1] % 64:
+            return x
+        T, E = x.shape
+        ctx.lora_x = torch.empty(T, E + X, dtype=x.dtype, device=x.device)
+        ctx.lora_x[:, :E].copy_(x)                                # (row move, no arithmetic)
+        return ctx.lora_x[:, :E]
+
+    def add_lora(self, rank=16, alpha=16, layers=('query', 'value', 'output'), dropout_p=0., adapter_names=None):
+        """Attach LoRA adapters (reference esm.py:495-543): every layer's `self_attn.{q,k,v,out}` named in `layers` becomes an
+        esme.lora.LoRA around the projection, with one (A, B) pair per name in `adapter_names` (default ['default']); A is initialised
+        like the reference's (Kaiming uniform), B with zeros, so fresh adapters leave the model's output unchanged.  Inference only:
+        `dropout_p` is stored (and written by save_lora) but never applied.  Refuses what cannot run the adapters: a precision other
+        than 'fast', quantised base weights, padded layouts (ESM2-35M), ranks outside 1 .. 64."""
+        from esme.lora import LoRA
+        wanted = set(layers)
+        assert len(wanted.difference({'query', 'value', 'key', 'output'})) == 0, 'layers must be a subset of {"query", "value", "key", "output"}'
+        if self.has_lora:
+            raise NotImplementedError('LoRA adapters are already attached to this model (a second set would wrap the first)')
+        if self.precision != 'fast':
+            raise NotImplementedError(f"precision {self.precision!r} has no LoRA adapter path: adapters run in precision 'fast' only")
+        if getattr(self, 'quantization', None) is not None:
+            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters)')
+        if self.padded:
+            raise NotImplementedError('LoRA adapters are not implemented for padded layouts (head dim 24 / a width that is not a multiple of 64: ESM2-35M)')
+        if not (1 <= int(rank) <= 64) or int(rank) != rank:
+            raise NotImplementedError(f'LoRA rank {rank}: integer ranks 1 .. 64 are served')
+        self.lora_kwargs = {'rank': rank, 'alpha': alpha, 'dropout_p': dropout_p,
+                            'layers': [long for long, _ in self._LORA_TARGETS if long in wanted], 'names': adapter_names}
+        for layer in self.layers:
+            att = layer.self_attn
+            for long, short in self._LORA_TARGETS:
+                if long in wanted:
+                    setattr(att, short, LoRA(getattr(att, short), rank=rank, alpha=alpha, dropout_p=dropout_p, names=adapter_names))
+            att._has_lora = True
+        self.__dict__['_lora_attached'] = True
+        self.mark_only_lora_as_trainable(adapter_names)
+        self.invalidate_graphs()
+        return self
+
+    def mark_only_lora_as_trainable(self, adapter_names=None):
+        from esme.lora import mark_only_lora_as_trainable
+        mark_only_lora_as_trainable(self, adapter_names)
+        return self
+
+    def lora_state_dict(self, adapter_names=None):
+        from esme.lora import lora_state_dict
+        return lora_state_dict(self, adapter_names)
+
+    def save_lora(self, path: str, adapter_names=None):
+        """Write the adapters (all, or those named) to a safetensors file in the reference's format (esm.py:564-585): the
+        `lora_A` / `lora_B` tensors under their state-dict keys, metadata rank / alpha / dropout_p / layers / names / format."""
+        from safetensors.torch import save_file
+        state = self.lora_state_dict(adapter_names)
+        assert len(state) > 0, 'No LoRA adapters found to save'
+        kw = self.lora_kwargs
+        names = adapter_names or kw['names'] or self.lora_names()
+        save_file({k: v.detach().contiguous() for k, v in state.items()}, path,
+                  {'rank': str(kw['rank']), 'alpha': str(kw['alpha']), 'dropout_p': str(kw['dropout_p']),
+                   'layers': ','.join(kw['layers']), 'names': ','.join(names), 'format': 'pt'})
+        return self
+
+    def load_lora(self, path: str, names=None):
+        """Attach the adapters of a file written by `save_lora` (this package's or the reference's) to a model loaded from the base
+        checkpoint (esm.py:587-608).  `names` is accepted for signature compatibility; as in the reference, every adapter of the file
+        is attached -- select per call with `lora_names=`."""
+        from safetensors import safe_open
+        with safe_open(path, framework='pt', device='cpu') as f:
+            md = f.metadata() or {}
+            tensors = {k: f.get_tensor(k) for k in f.keys()}
+        a = md['alpha']
+        self.add_lora(rank=int(md['rank']), alpha=int(a) if a.lstrip('-').isdigit() else float(a), dropout_p=float(md['dropout_p']),
+                      layers=md['layers'].split(','), adapter_names=md['names'].split(','))
+        own = self.state_dict()
+        unexpected = [k for k in tensors if k not in own]
+        assert len(unexpected) == 0, f'Expected LoRA keys in the model missing state_dict: {unexpected}'
+        missing = [k for k in self.lora_state_dict() if k not in tensors]
+        assert len(missing) == 0, f'LoRA keys of the model missing in the file: {missing}'
+        with torch.no_grad():
+            for k, t in tensors.items():
+                own[k].copy_(t)                                   # (bumps the version counter: derived weights are rebuilt)
+        self.invalidate_graphs()
+        return self
+
+    def mark_lmhead(self, trainable=True):
+        for p in self.lm_head.parameters():
+            p.requires_grad_(trainable)
+        return self
 
     # -- loading -------------------------------------------------------------------
     @classmethod

@@ -107,7 +107,7 @@ def masked_row_log_prob(model, token: torch.Tensor, local_pos: torch.Tensor, gra
     if getattr(model, 'precision', 'fast') in ('exact', 'half'):      # split-operand mode: fp32 log-probs of every row (the head needs the (hi, lo) pair), then pick
         lp = model.predict_log_prob(token.reshape(-1), (cu_lens, L))
         return lp[(torch.arange(B, dtype=torch.int64) * L + local_pos.to(torch.int64).cpu()).to(device)]
-    if graph:
+    if graph and not getattr(model, 'has_lora', False):       # (a model with LoRA adapters has no graph replay: it runs eagerly, all adapters applied)
         rep = model.graphed(token.reshape(-1), (cu_lens, L), 'forward_representation', clone=False)
     else:
         rep = model.forward_representation(token.reshape(-1), (cu_lens, L))

@@ -528,6 +528,26 @@ int esme_hip_attn_pool(const void* x, int64_t ldx, const int32_t* cu_lens, int B
 int esme_hip_relu_linear(const void* h, int64_t ldh, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
                          int64_t M, int N, int K, int dtype_f32, void* stream);
 
+/* ---- LoRA adapters in the packed forward (reference esme/lora.py LoRA.lora_forward) -----------------
+ * The low-rank delta of a projection rides in an extension K-tile of the GEMM that computes it: the operand row is [x | u]
+ * (X extra columns, lda = K + X or wider), the weight [W | s B | 0] (N, K + X), and esme_hip_gemm_bf16* is called with K + X.
+ * These two entry points fill u, the down-projection, for all adapters of that GEMM at once (their A matrices stacked to `rank` rows):
+ *   esme_hip_lora_down     u[t, j] = bf16(sum_k x[t, k] A[j, k])
+ *   esme_hip_lora_down_ln  u[t, j] = bf16(sum_k x[t, k] A[j, k] - mean_t c1[j] + sqrt(var_t + ln_eps) bA[j])
+ * The second serves a LayerNorm-folded GEMM, whose epilogue multiplies the accumulator by rstd_t: with A = bf16(gamma * A0),
+ * c1[j] = sum_k A[j, k] and bA[j] = sum_k beta[k] A0[j, k] it writes LN(x_t) . A0_j / rstd_t.  mean_t / var_t come from the same partial
+ * sums the GEMM consumes (esme_gemm_fusion_t.ln_partial: (ln_nblk, T, 2) fp32 {sum, sum of squares}, taken over ln_dim columns).
+ *  x: bf16 (T, E), row stride ldx;  A: bf16 (rank, E) contiguous;  u: bf16 (T, X), row stride ldu -- columns rank .. X-1 are written
+ *  as zeros, nothing outside the X columns is touched (u may be the columns E .. E+X-1 of the buffer that holds x);  c1, bA: fp32 (rank).
+ * Limits: E % 64 == 0, X % 64 == 0 (else ESME_ERR_UNSUPPORTED), X <= 256 in this build (else ESME_ERR_UNSUPPORTED), 0 < rank <= X,
+ * ldx >= E, ldu >= X, both multiples of 8, 16-byte aligned x, A, u (else ESME_ERR_ARG).  T = 0 is a no-op.  fp32 accumulation
+ * (v_mfma_f32_16x16x32_bf16), one rounding. */
+int esme_hip_lora_down(const void* x, int64_t ldx, const void* A, int rank, int64_t T, int E, int X, void* u, int64_t ldu,
+                       void* stream);
+int esme_hip_lora_down_ln(const void* x, int64_t ldx, const void* A, int rank, int64_t T, int E, int X, void* u, int64_t ldu,
+                          const float* ln_partial, int ln_nblk, int ln_dim, float ln_eps, const float* c1, const float* bA,
+                          void* stream);
+
 /* ---- 4-bit weight-only block quantisation ("esme-q4") ------------------------------
  * The reference delegates this to bitsandbytes.nn.Linear4bit (esme/esm.py:434-446,
  * :482-484, :915-946), a third-party CUDA library that is not vendored; the format here is
