@@ -593,7 +593,8 @@ int esme_hip_dequantize_8bit(const void* codes, const float* scale, int64_t N, i
  *  x:       (T, phys_dim) bf16, row stride ldx: the embedded tokens on entry (esme_hip_embed), the final-LayerNorm
  *           representation on exit (pad columns, if any, stay zero);
  *  pos:     int32 (T) in-sequence positions (esme_hip_seq_positions); cos / sin: (table_len, head_pad) bf16 tables;
- *  workspace: esme_hip_forward_workspace_bytes(desc, T) bytes, 16-byte aligned;
+ *  workspace: esme_hip_forward_workspace_bytes(desc, T) bytes, 16-byte aligned, no initialisation needed (padded layouts included:
+ *           every column that is read is written first);
  *  logits:  (T, vocab) bf16 with row stride ld_logits, or NULL for representations only.
  * Layer weights are the DERIVED copies the fast path uses: the fused (3*H*head_pad, phys_dim) q/k/v weight and the FFN
  * up weight scaled by the LayerNorm gain (W' = W diag(gamma), bf16) with c1 = rowsum(W'), c2 = W beta + bias (fp32);
@@ -674,7 +675,7 @@ int esme_hip_forward(const esme_model_desc_t* model, void* x, int64_t ldx, const
  *  x32:   fp32 (T, phys_dim), row stride ld32: the stream at the start (embedding rows; ESM-1b / 1v: token + learned-position sums);
  *  pair:  bf16 (T, 2 * phys_dim) = [hi | lo], row stride ld_pair: the final LayerNorm's output as the split-operand LM head reads it
  *         (pad columns, if any, are left as they are: pass zeros); rep32: the same in fp32 (T, phys_dim), row stride ld_rep, or NULL;
- *  workspace: esme_hip_forward_half_workspace_bytes(desc, T) bytes, 16-byte aligned.
+ *  workspace: esme_hip_forward_half_workspace_bytes(desc, T) bytes, 16-byte aligned, no initialisation needed.
  * Issues the launches of the module-by-module path (esme/attention.py forward_high_precision): bit-identical results.  No counterpart in
  * the reference (its arithmetic type is the constructor's dtype, esme/esm.py:132-141). */
 int64_t esme_hip_forward_half_workspace_bytes(const esme_model_desc_t* model, int64_t T);

@@ -659,3 +659,73 @@ def test_partition_properties_hypothesis():
                 seen.append(t)
             assert torch.equal(torch.sort(torch.cat(seen)).values, tokens)
     check()
+
+
+# ------------------------------------------------------------------ alignment of every 8- / 16-byte access is checked on the host
+
+_P = 1 << 20          # a 16-byte aligned fake device address: validation happens before anything is dereferenced or launched
+
+
+def _alignment_table():
+    """(entry point, valid arguments, {argument index: a value that breaks the alignment include/esme_hip.h states}).  The valid call passes
+    validation (it would launch); each variant must be refused on the host with ESME_ERR_ARG / ESME_ERR_UNSUPPORTED.
+    Not listed, because their kernels touch the operand one 2- or 4-byte element at a time: esme_hip_quantize_4bit (w), the cls / w_k operands of
+    esme_hip_attn_pool_fold, the output of esme_hip_attn_pool, esme_hip_softmax_rows*, esme_hip_seq_positions / esme_hip_seq_order."""
+    P = _P
+    cb = (ctypes.c_float * 16)()
+    return [
+        ('esme_hip_layernorm', [P, 64, P, P, P, 64, 4, 64, 1e-5], {0: P + 2, 1: 68, 4: P + 2, 5: 68}),
+        ('esme_hip_layernorm_f32', [P, 64, P, P, P, 64, 4, 64, 1e-5], {0: P + 4, 1: 66, 4: P + 2, 5: 68}),
+        ('esme_hip_layernorm_split', [P, 64, 0, 0, P, P, P, 128, 64, P, 64, 4, 64, 1e-5], {0: P + 4, 1: 66, 6: P + 2, 7: 132, 8: 68, 9: P + 4, 10: 66}),
+        ('esme_hip_layernorm_split_checked', [P, 128, 1, 64, P, P, P, 128, 64, P, 64, 4, 64, 1e-5, None], {0: P + 2, 1: 132, 3: 68, 6: P + 2}),
+        ('esme_hip_rotary_varlen', [P, P, 128, P, P, P, 4, 2, 64, 8], {0: P + 2, 1: P + 2, 2: 132}),
+        ('esme_hip_rotary_varlen_f16', [P, P, 128, P, P, P, 4, 2, 64, 8], {0: P + 2, 1: P + 2, 2: 132}),
+        ('esme_hip_rotary_split', [P, 512, 256, P, P, P, 4, 2, 64, 8], {0: P + 2, 1: 516, 2: 260}),
+        ('esme_hip_rotary_split_f16', [P, 512, 256, P, P, P, 4, 2, 64, 8], {0: P + 2, 1: 516, 2: 260}),
+        ('esme_hip_qk_norm_rotary', [P, P, 128, P, P, None, None, 1e-5, P, P, P, 4, 2, 64, 8], {0: P + 2, 1: P + 2, 2: 132}),
+        ('esme_hip_qk_norm_rotary_scaled', [P, P, 128, P, P, None, None, 1e-5, P, P, P, 4, 2, 64, 8, 0.18], {0: P + 2, 2: 132}),
+        ('esme_hip_qk_norm_rotary_f16', [P, P, 128, P, P, None, None, 1e-5, P, P, P, 4, 2, 64, 8], {0: P + 2, 2: 132}),
+        ('esme_hip_qk_norm_rotary_f16_guarded', [P, P, 128, P, P, None, None, 1e-5, P, P, P, 4, 2, 64, 8, None], {0: P + 2, 2: 132}),
+        ('esme_hip_qk_norm_rotary_f16_scaled', [P, P, 128, P, P, None, None, 1e-5, P, P, P, 4, 2, 64, 8, 0.18, None], {0: P + 2, 2: 132}),
+        ('esme_hip_attn_varlen_fwd', [P, P, P, 384, P, 128, P, 1, 8, 2, 64, 8, 0.125], {0: P + 2, 1: P + 8, 2: P + 2, 3: 388, 4: P + 2, 5: 130}),
+        ('esme_hip_attn_varlen_fwd_exact', [P, P, P, 384, P, 128, P, 1, 8, 2, 64, 8, 0.125], {0: P + 2, 3: 388, 4: P + 2, 5: 130}),
+        ('esme_hip_attn_varlen_fwd_split', [P, P, P, 768, 384, P, 256, 128, P, 1, 8, 2, 64, 8, 0.125, None], {0: P + 2, 3: 772, 4: 388, 5: P + 2, 6: 258, 7: 130}),          # (o: 8-byte stores, ld_o % 4)
+        ('esme_hip_attn_varlen_fwd_qkpair_f16', [P, P, P, 640, 384, P, 128, P, 1, 8, 2, 64, 8, 0.125, None], {0: P + 2, 3: 644, 4: 388, 5: P + 2, 6: 130}),
+        ('esme_hip_residual_f32', [P, 64, P, 64, 0.5, 0, P, 64, P, 4, 64], {0: P + 4, 1: 66, 2: P + 2, 3: 68, 6: P + 2, 7: 68}),
+        ('esme_hip_stream_operand', [P, 64, P, 128, 64, 1, P, 4, 64], {0: P + 4, 1: 66, 2: P + 2, 3: 132, 4: 68}),
+        ('esme_hip_stream_operand_scaled', [P, 64, P, 192, 128, 1, P, None, 0, 0, P, 4, 64], {0: P + 4, 2: P + 2, 3: 196, 4: 132, 6: P + 4}),
+        ('esme_hip_pair_to_f32', [P, 128, 64, 1, P, 64, 4, 64], {0: P + 2, 1: 132, 2: 68, 4: P + 4, 5: 66}),
+        ('esme_hip_row_sums', [P, 64, 4, 64, P], {0: P + 2, 1: 68}),
+        ('esme_hip_gather_rows', [P, 8, P, P, 4, 64], {0: P + 2, 3: P + 2}),
+        ('esme_hip_scatter_rows', [P, P, P, 8, 4, 64], {0: P + 2, 2: P + 2}),
+        ('esme_hip_segment_mean', [P, 64, P, 2, 64, P, 64, 0], {0: P + 2, 1: 68, 5: P + 2, 6: 68}),
+        ('esme_hip_attn_pool_fold', [P, 64, P, 64, 64, 4, 2, P], {7: P + 4}),                    # (cls / w_k: element-wise 2-byte loads)
+        ('esme_hip_attn_pool', [P, 64, P, 2, 8, 64, 4, 2, P, P, 1 << 20, P, 128, 0], {0: P + 2, 1: 68, 8: P + 4, 9: P + 4}),      # (out: element-wise stores)
+        ('esme_hip_relu_linear', [P, 64, P, 64, P, P, 8, 4, 8, 64, 0], {0: P + 2, 1: 68, 2: P + 2, 3: 68}),
+        ('esme_hip_lora_down', [P, 128, P, 8, 4, 64, 64, P, 128], {0: P + 2, 1: 132, 2: P + 2, 7: P + 2, 8: 132}),
+        ('esme_hip_gemm_bf16', [P, 64, P, P, None, 0, P, 64, 8, 64, 64, 0, 1.0], {0: P + 2, 1: 68, 2: P + 2, 3: P + 2}),
+        ('esme_hip_gemm_qkv_rotary', [P, 64, P, None, P, 192, 8, 192, 64, P, P, P, 64, 8, 128], {0: P + 2, 1: 68, 4: P + 2, 5: 196, 9: P + 2}),
+        ('esme_hip_dequantize_4bit', [P, P, 4, 64, cb, None, P, 64], {6: P + 2, 7: 68}),
+        ('esme_hip_quantize_8bit', [P, 64, 4, 64, P, P], {0: P + 2, 1: 68}),
+        ('esme_hip_dequantize_8bit', [P, P, 4, 64, None, P, 64], {5: P + 2, 6: 68}),
+        ('esme_hip_embed', [P, P, P, 4, 64, 33, -1, -1], {1: P + 2, 2: P + 2}),
+        ('esme_hip_embed_positions', [P, P, P, P, 2, P, 4, 64, 33, 70, -1], {1: P + 2, 2: P + 2, 5: P + 2}),
+        ('esme_hip_embed_positions_f32', [P, P, P, P, 2, P, 4, 64, 33, 70, -1], {1: P + 2, 2: P + 2, 5: P + 4}),
+    ]
+
+
+@pytest.mark.parametrize('name,args,bad', _alignment_table(), ids=[t[0] for t in _alignment_table()])
+def test_misaligned_pointer_or_stride_is_refused_before_any_launch(name, args, bad):
+    """For every entry point whose kernel uses 8- or 16-byte accesses: a pointer or a leading dimension that breaks the alignment the header
+    states returns ESME_ERR_ARG or ESME_ERR_UNSUPPORTED from the host-side checks -- never ESME_OK, and never ESME_ERR_LAUNCH (which would
+    mean the call got as far as the launch)."""
+    from esme import _hip
+    fn = getattr(_hip.load(), name)
+    missed = []
+    for i, v in bad.items():
+        a = list(args)
+        a[i] = v
+        code = fn(*a, None)
+        if code not in (-1, -2):
+            missed.append(f'argument {i} = {v:#x}: code {code} ({_hip.load().esme_hip_last_error()})')
+    assert not missed, f'{name}: not refused on the host: ' + '; '.join(missed)
