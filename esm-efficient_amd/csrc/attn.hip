@@ -26,18 +26,8 @@
 // than 2^8), so the common tile does no O-wide VALU pass.
 #include "common.h"
 #include "launch.h"
-#ifndef ESME_ATTN_CM4_ASM
-#define ESME_ATTN_CM4_ASM 0
-#endif
 #include "gemm.h"
 
-#ifndef ESME_ATTN_ABL           // lab builds only (timing ablations of attn_pp64_kernel, WRONG results; profiles/r05_attn_rowsum_ablation.txt):
-#define ESME_ATTN_ABL 0         // 1 = the two row-sum v_add per score pair dropped; 3 = ... and 4 MFMAs per phase on a ones fragment issued instead
-#endif                          // (what "row sums on the matrix pipe" would execute: VERDICT r4 item 3b)
-#ifndef ESME_ATTN_DMA0          // MFMA slots of a phase behind which this wave's two LDS-DMA pieces are issued (A/B builds)
-#define ESME_ATTN_DMA0 3
-#define ESME_ATTN_DMA1 11
-#endif
 #include <atomic>
 #include <type_traits>
 
@@ -45,6 +35,8 @@ namespace esme {
 
 static constexpr int QT = 128;   // query rows per workgroup per q-block (4 waves x 32)
 static constexpr int KT = 64;    // keys per tile
+// MFMA slots of a phase behind which a wave of attn_pp64_kernel issues its two LDS-DMA pieces
+static constexpr int kAttnDma0 = 3, kAttnDma1 = 11;
 
 struct AttnArgs {
     const u16* q; const u16* k; const u16* v; int64_t ld;
@@ -682,7 +674,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(const AttnSplitArgs 
 // no reference at all); the speculative pass against the FIRST tile's maximum stays (P = 2^(how far a later score beats that maximum): a
 // handful on real data) with the overflow test tightened to fp16's range -- a work item that trips it is redone with exact maxima (P <= 1).
 // QP && F16 (round 6): the no-reference form with a FIXED reference of 4 (log2 units) -- the score accumulators start at -4.0 (the C operand of each score block's
-// first MFMA: sixteen registers kept for the purpose; as an inline constant of the instruction only behind ESME_ATTN_CM4_ASM, see common.h), so P = 2^(s - 4) stays inside fp16 for scores up to 20 (13.9 in natural units: e^13.9 = 10^6 times the weight of a zero
+// first MFMA: sixteen registers kept for the purpose; the inline-constant spelling of the instruction was a lab build), so P = 2^(s - 4) stays inside fp16 for scores up to 20 (13.9 in natural units: e^13.9 = 10^6 times the weight of a zero
 // score).  A row whose scores go higher trips the overflow test (partial sum >= 3e4), a row whose sum falls below S * 2^-14 (its P values average below fp16's smallest normal
 // number) trips the vanished-sum test: both redo the work item with exact maxima, exactly as the bf16 form does at 1e30 / 1e-30.
 template <int NW, bool QP = false, int D = 64, bool F16 = false>
@@ -813,9 +805,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_pp64_kernel(const AttnArgs a)
     };
 
     f32x16 oacc[2][DB], sacc[2][2];
-#if ESME_ATTN_ABL & 2
-    f32x16 abl_l = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // ONE set for both blocks (a real kernel needs two: +32 registers)
-#endif
     u32x4 pw[2][2][2];                 // P of block bb as packed bf16: [bb][32-key block][16-key step]
     float mc[2], lrun[2];
     const float c = a.scale_log2, thr = a.thr;
@@ -848,11 +837,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_pp64_kernel(const AttnArgs a)
                 const int j = m - NPV, kbk = j & 1, ds = j >> 1;
                 if (ds == 0) {
                     if constexpr (QP && F16) {
-#if ESME_ATTN_CM4_ASM
-                        sacc[bm][kbk] = mfma_32x32x16_f16_cm4(fr[m % 3], qf[bm][ds]);     // starts at S0 = -4 (inline constant)
-#else
                         sacc[bm][kbk] = mfma_32x32x16<F16>(fr[m % 3], qf[bm][ds], zneg);   // starts at S0 = -4 (a register block kept for the purpose)
-#endif
                     } else {
                         const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                         sacc[bm][kbk] = mfma_32x32x16<F16>(fr[m % 3], qf[bm][ds], z);
@@ -864,12 +849,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_pp64_kernel(const AttnArgs a)
                 const int db = m % DB, ks = m / DB;
                 oacc[bm][db] = mfma_32x32x16<F16>(
                     fr[m % 3], __builtin_bit_cast(bf16x8, pw[bm][ks >> 1][ks & 1]), oacc[bm][db]);
-#if ESME_ATTN_ABL & 2
-                if (db == DB - 1) {          // the row-sum MFMA of this 16-key step: ones (32 x 16) times P^T
-                    const u32x4 ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-                    abl_l = mfma_32x32x16<F16>(__builtin_bit_cast(bf16x8, ones), __builtin_bit_cast(bf16x8, pw[bm][ks >> 1][ks & 1]), abl_l);
-                }
-#endif
             }
         };
         // P, packed to bf16, and four partial row sums of block bs against the reference maximum -nm.  Pair p covers
@@ -889,9 +868,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_pp64_kernel(const AttnArgs a)
         auto pair_sum_pack = [&](const int p, const float q0, const float q1) {
             const int kbk = p >> 3, r = (2 * p) & 15;
             pw[bs][kbk][r >> 3][(r & 7) >> 1] = pack16<F16>(q0, q1);
-#if !(ESME_ATTN_ABL & 1)
             if (p & 1) { ps2 += q0; ps3 += q1; } else { ps0 += q0; ps1 += q1; }
-#endif
         };
         auto softmax_slot = [&](const int m, const float nm) {      // pair step m = 0..15 (one per MFMA slot at head dim 64, two at 32)
             const float q0 = pa0, q1 = pa1;                  // P of pair m - 1
@@ -976,14 +953,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_pp64_kernel(const AttnArgs a)
         // overflow (inf / NaN included): the work item is redone exactly.  fp16 P ends at 65 504: a lane's partial sum below 3e4 bounds each of
         // its P values (the pack would have produced inf otherwise; those MFMAs are discarded with the redo)
         if (__any(!(psum < (F16 ? 3.0e4f : 1e30f)))) ovf = 1;
-#if ESME_ATTN_ABL
-        lrun[bs] += 1.0f;
-#if ESME_ATTN_ABL & 2
-        asm volatile("" : "+v"(abl_l));
-#endif
-#else
         lrun[bs] += psum;
-#endif
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -1060,11 +1030,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_pp64_kernel(const AttnArgs a)
                 const bool tail = t == nt - 1 && ragged;
                 const bool need_max = exact || (!QP && t == 0);
                 phase(I0{}, I1{}, need_max, tail, cur, prv, t * KT, [&](const int m) {
-                    if (KI == 2) { if (m == ESME_ATTN_DMA0 && pf_k) dma_piece(0, t + 3, kslot, 0); if (m == ESME_ATTN_DMA1 && pf_k) dma_piece(0, t + 3, kslot, KI - 1); }
+                    if (KI == 2) { if (m == kAttnDma0 && pf_k) dma_piece(0, t + 3, kslot, 0); if (m == kAttnDma1 && pf_k) dma_piece(0, t + 3, kslot, KI - 1); }
                     else if (m == NM / 2 - 1 && pf_k) dma_piece(0, t + 3, kslot, 0);
                 });
                 phase(I1{}, I0{}, need_max, tail, nxt, cur, t * KT, [&](const int m) {
-                    if (KI == 2) { if (m == ESME_ATTN_DMA0 && pf_v) dma_piece(1, t + 2, vslot, 0); if (m == ESME_ATTN_DMA1 && pf_v) dma_piece(1, t + 2, vslot, KI - 1); }
+                    if (KI == 2) { if (m == kAttnDma0 && pf_v) dma_piece(1, t + 2, vslot, 0); if (m == kAttnDma1 && pf_v) dma_piece(1, t + 2, vslot, KI - 1); }
                     else if (m == NM / 2 - 1 && pf_v) dma_piece(1, t + 2, vslot, 0);
                 });
             } else {
@@ -1534,353 +1504,6 @@ __global__ __launch_bounds__(256, 2) void attn_sb_kernel(const AttnSplitArgs sa)
     }
 }
 
-#ifdef ESME_ATTN_W4          // lab build only (tools/lab/build_alt.sh attn.hip ... with -DESME_ATTN_W4): measured slower, see the note below
-// =============================================================================================
-// Head dim 64, ONE wave per SIMD (round 4): 4 waves per workgroup, each wave owns FOUR 32-row query blocks (128 rows; 512 per
-// workgroup) and the whole 512-entry register file of its SIMD (O^T accumulators and the Q fragments in the accumulator half).
-// Same math, LDS images and data path as attn_pp64_kernel (K / V tiles by counted LDS-DMA into a ring of four slots, V^T fragments by
-// ds_read_b64_tr_b16, speculative softmax on pre-scaled q); what changes is the amount of work per fragment and per barrier:
-//   * every K / V^T fragment is read ONCE per key tile into registers and feeds FOUR MFMAs (one per query block): 24 LDS
-//     instructions per 64 MFMAs instead of ~1.5 per MFMA, one barrier per 64 MFMAs instead of per 32;
-//   * the software pipeline rotates over the four blocks: phase (b, t) runs softmax(b, t) on the VALU while the matrix pipe does
-//     O^T(b-1) += V^T P(b-1)^T and S^T(b+1) = K Q_{b+1}^T -- 16 x { 1 MFMA, 1 score pair: 2 v_exp + 2 v_add + 1 v_cvt_pk };
-//     the K fragment set is replaced in place (tile t+1) behind the MFMAs of phase (2, t), the V^T set behind those of (0, t+1).
-// MEASURED (profiles/r04_attn_w4_lab.txt; bit-identical to attn_pp64_kernel<4, true> on every batch): 237 vs 183 us at S = 500, 246 vs
-// 194 at S = 1 002, 663 vs 546 at S = 2 000, 504 vs 355 on the proteome-like batch -- 20-40 % SLOWER.  Ablations at S = 2 000: without
-// the in-loop LDS-DMA 607 us, without the fragment reloads 615: the core {1 MFMA, 2 v_exp, 2 v_add, 1 v_cvt_pk} stream of ONE wave runs
-// ~64 cycles per MFMA, which is what tools/lab/mfma_issue_probe.hip predicts (profiles/r02_mfma_issue_probe.txt: this mix at F = 5 costs
-// 49.7 cycles per MFMA with one wave per SIMD and 38.9 with two -- a second wave hides the VALU issue of the first behind its own MFMA;
-// at head dim 128, where the CDNA4 guide's one-wave kernel reaches 50-56 %, every MFMA carries half the softmax work).  Kept out of the
-// shipped library; not a candidate.
-// q must arrive pre-multiplied by softmax_scale * log2(e) (esme_attn_opts_t.q_prescaled; the QKV epilogue / the ESM-C q/k pass do
-// it): P = exp2(score) with no reference maximum; a row sum that overflows or vanishes sends the work item through the classic
-// online softmax (the same code with need_max), exactly as in attn_pp64_kernel<NW, true>.
-// The MFMAs are inline asm with the accumulator classes pinned -- O^T and Q in the AGPR half ("a"), scores in arch VGPRs ("v":
-// the softmax reads them; a VALU instruction cannot read an AGPR) -- hipcc's own placement of the builtin copies accumulators
-// between the halves.  Hazards: an MFMA result is read by the VALU at the earliest two MFMAs (>= 64 cycles) after the MFMA that
-// wrote it (kbk-minor order of the S^T steps; the need_max path pads with s_nop); an accumulate chain needs no wait state.
-#ifndef ESME_W4_ABL
-#define ESME_W4_ABL 0           // timing ablations (wrong results): 1 = no softmax VALU, 2 = no LDS-DMA inside the loop, 4 = no fragment reloads
-#endif
-#define ESME_MFMA32_VA(ACC, AF, BF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(ACC) : "v"(AF), "a"(BF))
-#define ESME_MFMA32_VA0(ACC, AF, BF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=v"(ACC) : "v"(AF), "a"(BF))
-#define ESME_MFMA32_AV(ACC, AF, BF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(ACC) : "v"(AF), "v"(BF))
-__global__ __launch_bounds__(256, 1) void attn_w4_kernel(const AttnArgs a) {
-    constexpr int D = 64, DS = 4, NW = 4, NT = 256, QB = 4;
-    constexpr int K_BYTES = KT * D * 2;          // 8 KB
-    constexpr int SLOT = K_BYTES + D * 128;
-    constexpr int ROWS = NW * QB * 32;           // 512
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, hi = lane >> 5;
-    const unsigned int xcd = blockIdx.x & 7u, bi = blockIdx.x >> 3;
-    const int qt = (int)(bi % (unsigned int)a.nqt);
-    const unsigned int hb = (bi / (unsigned int)a.nqt) * 8u + xcd;
-    if (hb >= (unsigned int)a.nhb) return;
-    const int h = (int)(hb % (unsigned int)a.H), bi_seq = (int)(hb / (unsigned int)a.H);
-    const int b = a.order ? a.order[bi_seq] : bi_seq;
-    const int s0 = a.cu[b], S = a.cu[b + 1] - s0;
-    const int q0 = qt * ROWS;
-    if (q0 >= S) return;
-
-    const unsigned int ld = (unsigned int)a.ld;
-    const u16* qb = a.q + (int64_t)s0 * a.ld + h * D;
-    const unsigned int kv_bytes = ((unsigned int)(S - 1) * ld + D) * 2u;
-    auto make_rsrc = [&](const u16* p) -> u32x4 {
-        const uint64_t v = (uint64_t)(uintptr_t)p;
-        return u32x4{(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v),
-                     (unsigned int)__builtin_amdgcn_readfirstlane((int)((unsigned int)(v >> 32) & 0xffffu)),
-                     (unsigned int)__builtin_amdgcn_readfirstlane((int)kv_bytes), 0x00020000u};
-    };
-    const u32x4 krs = make_rsrc(a.k + (int64_t)s0 * a.ld + h * D);
-    const u32x4 vrs = make_rsrc(a.v + (int64_t)s0 * a.ld + h * D);
-    auto dma16 = [&](const u32x4 rs, const unsigned int voff, const char* dst) {
-        const unsigned int d = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(uintptr_t)dst);
-        unsigned int keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(d), "s"(rs) : "memory");
-    };
-
-    // ---- Q fragments of the wave's four q-blocks (B operand of S^T), kept in the accumulator half
-    bf16x8 qf[QB][DS];
-    const int wrow0 = q0 + wave * (QB * 32);
-    const bool wave_active = wrow0 < S;
-#pragma unroll
-    for (int bb = 0; bb < QB; ++bb) {
-        const int qr = wrow0 + bb * 32 + l31;
-        const unsigned int qc = qr < S ? qr : S - 1;
-#pragma unroll
-        for (int ds = 0; ds < DS; ++ds)
-            qf[bb][ds] = *reinterpret_cast<const bf16x8*>(qb + (qc * ld + ds * 16 + hi * 8));
-    }
-
-    constexpr int KI = 8 / NW;                                   // 2 DMA instructions per wave per K (or V) tile
-    const unsigned int tile_bytes = (unsigned int)KT * ld * 2u;
-    unsigned int kg0, vg0;
-    {
-        const int r = wave * 8 + (lane >> 3), pch = lane & 7;
-        kg0 = ((unsigned int)r * ld + ((pch ^ kswz<D>(r)) * 8)) * 2u;
-        vg0 = ((unsigned int)r * ld + ((pch ^ (((r >> 1) & 1) << 2)) * 8)) * 2u;
-    }
-    const unsigned int kg_step = (unsigned int)(NW * 8) * ld * 2u;
-    auto dma_piece = [&](const unsigned int rs_sel, const int tile, char* slot, const int i) {
-        if (rs_sel == 0) dma16(krs, (unsigned int)tile * tile_bytes + kg0 + i * kg_step, slot + (i * NW + wave) * 1024);
-        else dma16(vrs, (unsigned int)tile * tile_bytes + vg0 + i * kg_step, slot + K_BYTES + (i * NW + wave) * 1024);
-    };
-    auto dma_k = [&](int tile, char* slot) {
-#pragma unroll
-        for (int i = 0; i < KI; ++i) dma_piece(0, tile, slot, i);
-    };
-    auto dma_v = [&](int tile, char* slot) {
-#pragma unroll
-        for (int i = 0; i < KI; ++i) dma_piece(1, tile, slot, i);
-    };
-
-    const int krow_perm = (l31 & 3) | (((l31 >> 3) & 1) << 2) | (((l31 >> 2) & 1) << 3) | (l31 & 16);
-    int kfo[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) kfo[i] = krow_perm * 128 + (((i * 2 + hi) ^ ((krow_perm >> 1) & 7)) << 4);
-    int vb[2];
-    {
-        const int j = (lane & 15) >> 2, p = lane & 3, gsel = (lane >> 4) & 1;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) vb[db] = K_BYTES + (hi * 8 + j) * 128 + ((db ^ (j >> 1)) * 64) + gsel * 32 + p * 8;
-    }
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    auto vfrag = [&](const char* Vs, const int db, const int ks) -> bf16x8 {
-        typedef __attribute__((address_space(3))) s16x4* ltr_t;
-        const char* p = Vs + vb[db] + ks * 2048;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ltr_t)(p));
-        const s16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ltr_t)(p + 512));
-        return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
-    auto kfrag = [&](const char* Ks, const int kbk, const int ds) -> bf16x8 {
-        return *reinterpret_cast<const bf16x8*>(Ks + kbk * 4096 + kfo[ds]);
-    };
-
-    f32x16 oacc[QB][2];                // O^T of the four blocks: accumulator half
-    f32x16 sacc[2][2];                 // scores: set b & 1 of block b, [32-key block]
-    u32x4 pw[2][2][2];                 // P as packed bf16: set b & 1, [32-key block][16-key step]
-    bf16x8 kfr[2][4], vfr[2][4];       // the K fragment set [kbk][ds] and the V^T set [db][ks] of the tiles in use
-    float mc[QB], lrun[QB];
-    const float thr = a.thr;
-    int ovf = 0;
-
-    using std::integral_constant;
-    // One phase: softmax of block B on its finished scores, interleaved with the 16 MFMAs O^T(B-1) += V^T P(B-1)^T (m < 8) and
-    // S^T(B+1) = K Q^T (m >= 8).  RK / RV: this is the last phase that uses the K / V^T fragment set -- each fragment is
-    // replaced in place (from Kn / Vn, the next tile's slots) right behind the MFMA that used it last.
-    auto phase = [&](auto B_, const bool need_max, const bool tail, const int kv0, auto RK_, const char* Kn, auto RV_, const char* Vn, auto&& hook) __attribute__((always_inline)) {
-        constexpr int B = decltype(B_)::value, bs = B, bp = (B + 3) & 3, bq = (B + 1) & 3;
-        constexpr bool RK = decltype(RK_)::value, RV = decltype(RV_)::value;
-        constexpr int ss = bs & 1, sq = bq & 1, sp = bp & 1;          // register sets
-        auto mfma_step = [&](const int m) {
-            if (m < 8) {
-                const int db = m & 1, ks = m >> 1;
-                ESME_MFMA32_AV(oacc[bp][db], vfr[db][ks], pw[sp][ks >> 1][ks & 1]);
-                if constexpr (RV && !(ESME_W4_ABL & 4)) vfr[db][ks] = vfrag(Vn, db, ks);
-            } else {
-                const int j = m - 8, kbk = j & 1, ds = j >> 1;
-                if (ds == 0) ESME_MFMA32_VA0(sacc[sq][kbk], kfr[kbk][ds], qf[bq][ds]);
-                else ESME_MFMA32_VA(sacc[sq][kbk], kfr[kbk][ds], qf[bq][ds]);
-                if constexpr (RK && !(ESME_W4_ABL & 4)) kfr[kbk][ds] = kfrag(Kn, kbk, ds);
-            }
-        };
-        float ps0, ps1, ps2, ps3;
-        float pa0 = 0.f, pa1 = 0.f;
-        auto pair_sum_pack = [&](const int p, const float q0_, const float q1_) {
-            const int kbk = p >> 3, r = (2 * p) & 15;
-            pw[ss][kbk][r >> 3][(r & 7) >> 1] = pack_bf16(q0_, q1_);
-            if (p & 1) { ps2 += q0_; ps3 += q1_; } else { ps0 += q0_; ps1 += q1_; }
-        };
-        auto softmax_slot = [&](const int m) {
-            const float q0_ = pa0, q1_ = pa1;
-            const int kb2 = m >> 3, r2 = (2 * m) & 15;
-            pa0 = __builtin_amdgcn_exp2f(sacc[ss][kb2][r2]);
-            pa1 = __builtin_amdgcn_exp2f(sacc[ss][kb2][r2 + 1]);
-            if (m >= 1) pair_sum_pack(m - 1, q0_, q1_);
-            const int pk = m >= 1 ? m - 1 : 0, kbk = pk >> 3, r = (2 * pk) & 15;
-            asm volatile("" : "+v"(pw[ss][kbk][r >> 3]), "+v"(ps0), "+v"(ps1), "+v"(ps2), "+v"(ps3), "+v"(pa0), "+v"(pa1));
-        };
-        if (tail) {
-            int lim = S - kv0 - 8 * hi;
-            asm volatile("" : "+v"(lim));
-#pragma unroll
-            for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (kbk * 32 + 16 * (r >> 3) + (r & 7) >= lim) sacc[ss][kbk][r] = -1e30f;
-        }
-        if (need_max) {                      // classic online softmax (the redo pass): exact row maximum, subtracted before the pipelined region
-            asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // the last S^T MFMA of the previous phase must have written its scores
-            float tmax = sacc[ss][0][0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, sacc[ss][0][r]);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, sacc[ss][1][r]);
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-            const float tmc = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-            if (__any(tmc > mc[bs] + thr)) {
-                const float mn = fmaxf(mc[bs], tmc);
-                const float alpha = __builtin_amdgcn_exp2f(mc[bs] - mn);
-                mc[bs] = mn;
-                lrun[bs] *= alpha;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[bs][i][r] *= alpha;
-            }
-            const float mref = mc[bs];
-#pragma unroll
-            for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc[ss][kbk][r] -= mref;
-        }
-        ps0 = ps1 = ps2 = ps3 = 0.f;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-            mfma_step(m);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(ESME_W4_ABL & 1)) softmax_slot(m);
-            if constexpr (!(ESME_W4_ABL & 2)) hook(m);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        pair_sum_pack(15, pa0, pa1);
-        const float psum = (ps0 + ps1) + (ps2 + ps3);
-        if (__any(!(psum < 1e30f))) ovf = 1;
-        lrun[bs] += psum;
-    };
-    using I0 = integral_constant<int, 0>; using I1 = integral_constant<int, 1>; using I2 = integral_constant<int, 2>; using I3 = integral_constant<int, 3>;
-    using YES = integral_constant<bool, true>; using NO = integral_constant<bool, false>;
-
-    const int nt = (S + KT - 1) / KT;
-    bool exact = !a.spec;
-    for (;;) {
-#pragma unroll
-        for (int bb = 0; bb < QB; ++bb) {
-            mc[bb] = -1e30f; lrun[bb] = wave_active ? 0.f : 1.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oacc[bb][i][r] = 0.f;
-        }
-#pragma unroll
-        for (int st = 0; st < 2; ++st)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc[st][i][r] = 0.f;
-#pragma unroll
-                for (int s_ = 0; s_ < 2; ++s_) pw[st][i][s_] = u32x4{0u, 0u, 0u, 0u};
-            }
-        dma_k(0, smem);
-        dma_v(0, smem);
-        if (nt > 1) { dma_k(1, smem + SLOT); dma_v(1, smem + SLOT); }
-        if (nt > 2) dma_k(2, smem + 2 * SLOT);
-        {
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            char* v3 = smem + 3 * SLOT + K_BYTES;
-#pragma unroll
-            for (int i = 0; i < (D * 128) / (NT * 16); ++i) *reinterpret_cast<u32x4*>(v3 + (i * NT + tid) * 16) = z;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // (the Q fragments re-defined while no load is in flight: hipcc's wait-count pass otherwise guards their first uses in
-        // the loop with vmcnt(3..0), which drains the tile prefetch issued a few instructions earlier -- see attn_pp64_kernel)
-#pragma unroll
-        for (int bb = 0; bb < QB; ++bb)
-            asm volatile("" : "+a"(qf[bb][0]), "+a"(qf[bb][1]), "+a"(qf[bb][2]), "+a"(qf[bb][3]) : : "memory");
-        __syncthreads();
-        if (wave_active) {
-            // fragment sets: K(0); V^T of slot 3 (zeros: phase (0, 0) multiplies it by P = 0); S^T(b0, tile 0)
-#pragma unroll
-            for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-                for (int ds = 0; ds < DS; ++ds) kfr[kbk][ds] = kfrag(smem, kbk, ds);
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) vfr[db][ks] = vfrag(smem + 3 * SLOT, db, ks);
-#pragma unroll
-            for (int ds = 0; ds < DS; ++ds)
-#pragma unroll
-                for (int kbk = 0; kbk < 2; ++kbk) {
-                    if (ds == 0) ESME_MFMA32_VA0(sacc[0][kbk], kfr[kbk][ds], qf[0][ds]);
-                    else ESME_MFMA32_VA(sacc[0][kbk], kfr[kbk][ds], qf[0][ds]);
-                }
-        }
-        const bool ragged = (S & (KT - 1)) != 0;
-        for (int t = 0; t < nt; ++t) {
-            const bool pf_k = t + 3 < nt, pf_v = t + 2 < nt;
-            char* kslot = smem + ((t + 3) & 3) * SLOT;
-            char* vslot = smem + ((t + 2) & 3) * SLOT;
-            if (wave_active) {
-                const char* cur = smem + (t & 3) * SLOT;
-                const char* nxt = smem + ((t + 1) & 3) * SLOT;
-                const bool tail = t == nt - 1 && ragged;
-                const bool need_max = exact;
-                // phase (0, t): V^T set V(t-1) -> V(t) in place
-                phase(I0{}, need_max, tail, t * KT, NO{}, nxt, YES{}, cur, [&](const int m) { if (m == 5 && pf_k) dma_piece(0, t + 3, kslot, 0); });
-                phase(I1{}, need_max, tail, t * KT, NO{}, nxt, NO{}, cur, [&](const int m) { if (m == 5 && pf_k) dma_piece(0, t + 3, kslot, 1); });
-                // phase (2, t): K set K(t) -> K(t+1) in place
-                phase(I2{}, need_max, tail, t * KT, YES{}, nxt, NO{}, cur, [&](const int m) { if (m == 5 && pf_v) dma_piece(1, t + 2, vslot, 0); });
-                phase(I3{}, need_max, tail, t * KT, NO{}, nxt, NO{}, cur, [&](const int m) { if (m == 5 && pf_v) dma_piece(1, t + 2, vslot, 1); });
-            } else {
-                if (pf_k) dma_k(t + 3, kslot);
-                if (pf_v) dma_v(t + 2, vslot);
-            }
-            if (t + 3 < nt) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(2 * KI) : "memory");
-            else if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(KI) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        if (wave_active) {                          // drain: O^T(b3) += V(nt-1) P(b3, nt-1)  (the V^T set still holds V(nt-1))
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                for (int db = 0; db < 2; ++db) ESME_MFMA32_AV(oacc[3][db], vfr[db][ks], pw[1][ks >> 1][ks & 1]);
-        }
-        if (!exact) {
-#pragma unroll
-            for (int bb = 0; bb < QB; ++bb)
-                if (__any(!(lrun[bb] > 1e-30f))) ovf = 1;
-        }
-        if (exact || !__syncthreads_or(ovf)) break;
-        exact = true;
-        ovf = 0;
-    }
-    if (!wave_active) return;
-
-    // ---- epilogue: normalise, transpose through a wave-private LDS slab (4 KB per wave in a slot no wave reads any more), whole rows out
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");           // the drain MFMAs have written O^T
-    char* slab = smem + ((nt + 1) & 3) * SLOT + wave * 4096;
-#pragma unroll
-    for (int bb = 0; bb < QB; ++bb) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lrun[bb]), __float_as_uint(lrun[bb]), false, false);
-        const float inv = 1.0f / (__uint_as_float(sw[0]) + __uint_as_float(sw[1]));
-        if (bb) __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 pk = {pack_bf16(oacc[bb][db][4 * g] * inv, oacc[bb][db][4 * g + 1] * inv),
-                            pack_bf16(oacc[bb][db][4 * g + 2] * inv, oacc[bb][db][4 * g + 3] * inv)};
-                *reinterpret_cast<u32x2*>(slab + l31 * 128 + (((db * 4 + g) ^ (l31 & 7)) << 4) + hi * 8) = pk;
-            }
-        __builtin_amdgcn_wave_barrier();
-        const int rbase = wrow0 + bb * 32;
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int r = it * 8 + (lane >> 3), ch = lane & 7;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(slab + r * 128 + ((ch ^ (r & 7)) << 4));
-            if (rbase + r < S) *reinterpret_cast<u32x4*>(a.o + (int64_t)(s0 + rbase + r) * a.ldo + h * D + ch * 8) = v;
-        }
-    }
-}
-
-#endif  // ESME_ATTN_W4
-
 }  // namespace esme
 
 using namespace esme;
@@ -1890,14 +1513,7 @@ static int launch_pp64(AttnArgs& a, int B, int max_len, hipStream_t s) {
     constexpr int smem = 4 * (KT * D * 2 + D * 128);
     auto kern = attn_pp64_kernel<NW, QP, D, F16>;
     static std::atomic<unsigned long long> done{0ull};         // dynamic-LDS attribute: per (kernel, device)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-            return fail(ESME_ERR_LAUNCH, "attn: cannot raise the dynamic LDS limit");
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = raise_dynamic_lds(done, kern, smem, "attn")) return rc;
     a.nqt = (max_len + NW * 64 - 1) / (NW * 64);
     const int64_t blocks = (int64_t)a.nqt * (((int64_t)a.H * B + 7) / 8) * 8;
     if (blocks > 0x7fffffffLL) return fail(ESME_ERR_UNSUPPORTED, "attn: grid too large");
@@ -1910,42 +1526,13 @@ static int launch_sb(AttnSplitArgs& sa, int B, int max_len, hipStream_t s) {
     constexpr int smem = 3 * ((QKP ? 2 : 1) * KT * D * 2 + D * 128);
     auto kern = attn_sb_kernel<D, F16, QKP, QP>;
     static std::atomic<unsigned long long> done{0ull};         // dynamic-LDS attribute: per (kernel, device)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-            return fail(ESME_ERR_LAUNCH, "attn: cannot raise the dynamic LDS limit");
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = raise_dynamic_lds(done, kern, smem, "attn")) return rc;
     sa.a.nqt = (max_len + 127) / 128;
     const int64_t blocks = (int64_t)sa.a.nqt * (((int64_t)sa.a.H * B + 7) / 8) * 8;
     if (blocks > 0x7fffffffLL) return fail(ESME_ERR_UNSUPPORTED, "attn: grid too large");
     hipLaunchKernelGGL(kern, dim3((unsigned int)blocks), dim3(256), smem, s, sa);
     return check_launch("attn_varlen_fwd");
 }
-
-#ifdef ESME_ATTN_W4
-static int launch_w4(AttnArgs& a, int B, int max_len, hipStream_t s) {
-    constexpr int smem = 4 * (KT * 64 * 2 + 64 * 128);
-    auto kern = attn_w4_kernel;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-            return fail(ESME_ERR_LAUNCH, "attn: cannot raise the dynamic LDS limit");
-        done.fetch_or(bit, std::memory_order_release);
-    }
-    a.nqt = (max_len + 511) / 512;
-    const int64_t blocks = (int64_t)a.nqt * (((int64_t)a.H * B + 7) / 8) * 8;
-    if (blocks > 0x7fffffffLL) return fail(ESME_ERR_UNSUPPORTED, "attn: grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned int)blocks), dim3(256), smem, s, a);
-    return check_launch("attn_varlen_fwd");
-}
-
-#endif
 
 // The generic and split kernels take the sequence from grid z (at most 65 535 per launch: more run as several launches) and address
 // rows inside one sequence with 32-bit element offsets (row * ld_qkv + column, row < max_len + one row tile).  Checked before any launch:
@@ -1966,6 +1553,25 @@ static int generic_launch_ok(int64_t ld_qkv, int max_len, int rows, int B, const
     return ESME_OK;
 }
 
+// The checks that open all three attention entries, under the entry's message prefix `pre`: sizes, then the empty-batch return
+// (*empty set, ESME_OK), null pointers, the entry's own stride / pair-offset condition (`strides_ok`, named `strides_what` in the
+// message), alignment, max_len / H.  The caller returns at once when the result is non-zero or *empty is set.
+static int attn_entry_checks(const char* pre, const void* q, const void* k, const void* v, const void* o, const int32_t* cu_lens, int B,
+                             int64_t T, int H, int d, int max_len, bool strides_ok, const char* strides_what, bool* empty) {
+    auto bad = [&](const char* what) {
+        snprintf(error_buffer(), kErrorBufferSize, "%s: %s", pre, what);
+        return ESME_ERR_ARG;
+    };
+    *empty = false;
+    if (!(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0)) return bad("bad sizes");
+    if (T == 0 || B == 0) { *empty = true; return ESME_OK; }
+    if (!(q && k && v && o && cu_lens)) return bad("null pointer");
+    if (!strides_ok) return bad(strides_what);
+    if (!(aligned16(q) && aligned16(k) && aligned16(v) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0)) return bad("misaligned");
+    if (!(max_len > 0 && H <= 65535)) return bad("max_len must be > 0, H <= 65535");
+    return ESME_OK;
+}
+
 // (per-call options, esme_attn_opts_t: no process-global tuning state; NULL = the defaults below)
 static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv, void* o, int64_t ld_o, const int32_t* cu_lens,
                     int B, int64_t T, int H, int d, int max_len, float softmax_scale, void* stream, bool exact,
@@ -1975,14 +1581,10 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
     const int g_force_qb = opts ? opts->q_blocks : 0;          // first-generation kernel: q-blocks per wave (0 = heuristic)
     const float g_attn_thr = opts ? opts->defer_max_thr : 8.0f;   // defer-max threshold, log2 units
     const int g_attn_spec = opts ? opts->speculative : 1;      // speculative softmax in the ping-pong kernel
-    ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0, "attn: bad sizes");
-    if (T == 0 || B == 0) return ESME_OK;
-    ESME_CHECK_ARG(q && k && v && o && cu_lens, "attn: null pointer");
-    ESME_CHECK_ARG(ld_qkv % 8 == 0 && ld_qkv >= (int64_t)H * d && ld_o % 4 == 0 && ld_o >= (int64_t)H * d,
-                   "attn: bad row strides");
-    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0,
-                   "attn: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535, "attn: max_len must be > 0, H <= 65535");
+    bool empty;
+    if (const int rc = attn_entry_checks("attn", q, k, v, o, cu_lens, B, T, H, d, max_len,
+                                         ld_qkv % 8 == 0 && ld_qkv >= (int64_t)H * d && ld_o % 4 == 0 && ld_o >= (int64_t)H * d,
+                                         "bad row strides", &empty); rc || empty) return rc;
     // q_prescaled: q already carries softmax_scale * log2(e) (esme_gemm_fusion_t.q_scale): every kernel then runs with c = 1, and
     // the 4-wave head-dim-64 kernel in its no-reference-maximum form
     const bool f16 = opts && opts->f16;                         // fp16 operands: speculative / defer-max passes bounded to fp16's range (see the kernels)
@@ -2012,9 +1614,6 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
         // (one workgroup per CU) from S = 130 to S = 2 000; the 8-wave form stays behind the tuning hook.
         const int nw = g_attn_variant == 8 ? 8 : 4;
         if (f16) return qp ? launch_pp64<4, true, 64, true>(a, B, max_len, s) : launch_pp64<4, false, 64, true>(a, B, max_len, s);
-#ifdef ESME_ATTN_W4
-        if (qp && g_attn_variant == 16) return launch_w4(a, B, max_len, s);          // one wave per SIMD, four q-blocks per wave (lab build)
-#endif
         if (qp && nw == 4) return launch_pp64<4, true>(a, B, max_len, s);
         return nw == 8 ? launch_pp64<8>(a, B, max_len, s) : launch_pp64<4>(a, B, max_len, s);
     }
@@ -2032,8 +1631,7 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
     if (const int rc = generic_launch_ok(ld_qkv, max_len, rows, B, a.order, "attn")) return rc;
     const hipStream_t s0 = s;
     // sequence index on grid z (at most 65 535): chunks of sequences, each with cu_lens advanced to its first sequence
-    for (int b0 = 0; b0 < B; b0 += kMaxGridZ) {
-        const int nb = B - b0 < kMaxGridZ ? B - b0 : kMaxGridZ;
+    return for_sequence_chunks(B, kMaxGridZ, [&](int b0, int nb) {
         AttnArgs ac = a;
         ac.cu = cu_lens + b0;
         ac.nhb = H * nb;
@@ -2053,9 +1651,8 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
             ESME_ATTN(128)
         }
 #undef ESME_ATTN
-        if (const int rc = check_launch("attn_varlen_fwd")) return rc;
-    }
-    return ESME_OK;
+        return check_launch("attn_varlen_fwd");
+    });
 }
 
 template <int D, bool F16 = false, bool QKP = false>
@@ -2064,38 +1661,27 @@ static int launch_split(const AttnSplitArgs& sa, int B, int max_len, hipStream_t
     auto kern = attn_split_kernel<D, F16, QKP>;
     if (smem >= 64 * 1024) {
         static std::atomic<unsigned long long> done{0ull};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(done.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-                return fail(ESME_ERR_LAUNCH, "attn_split: cannot raise the dynamic LDS limit");
-            done.fetch_or(bit, std::memory_order_release);
-        }
+        if (const int rc = raise_dynamic_lds(done, kern, smem, "attn_split")) return rc;
     }
     // sequence index on grid z (at most 65 535): chunks of sequences, each with cu_lens advanced to its first sequence
-    for (int b0 = 0; b0 < B; b0 += kMaxGridZ) {
-        const int nb = B - b0 < kMaxGridZ ? B - b0 : kMaxGridZ;
+    return for_sequence_chunks(B, kMaxGridZ, [&](int b0, int nb) {
         AttnSplitArgs sc = sa;
         sc.a.cu = sa.a.cu + b0;
         sc.a.nhb = sa.a.H * nb;
         const dim3 grid((unsigned int)((max_len + QT - 1) / QT), (unsigned int)sa.a.H, (unsigned int)nb);
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, sc);
-        if (const int rc = check_launch("attn_varlen_fwd_split")) return rc;
-    }
-    return ESME_OK;
+        return check_launch("attn_varlen_fwd_split");
+    });
 }
 
 extern "C" int esme_hip_attn_varlen_fwd_split(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t lo_qkv, void* o,
                                               int64_t ld_o, int64_t lo_o, const int32_t* cu_lens, int B, int64_t T, int H, int d,
                                               int max_len, float softmax_scale, const int32_t* seq_order, void* stream) {
-    ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0, "attn_split: bad sizes");
-    if (T == 0 || B == 0) return ESME_OK;
-    ESME_CHECK_ARG(q && k && v && o && cu_lens, "attn_split: null pointer");
-    ESME_CHECK_ARG(ld_qkv % 8 == 0 && lo_qkv % 8 == 0 && lo_qkv > 0 && ld_o % 4 == 0 && lo_o % 4 == 0 && lo_o >= (int64_t)H * d &&
-                   ld_o >= lo_o + (int64_t)H * d, "attn_split: bad row strides / pair offsets");
-    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0, "attn_split: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535, "attn_split: max_len must be > 0, H <= 65535");
+    bool empty;
+    if (const int rc = attn_entry_checks("attn_split", q, k, v, o, cu_lens, B, T, H, d, max_len,
+                                         ld_qkv % 8 == 0 && lo_qkv % 8 == 0 && lo_qkv > 0 && ld_o % 4 == 0 && lo_o % 4 == 0 &&
+                                             lo_o >= (int64_t)H * d && ld_o >= lo_o + (int64_t)H * d,
+                                         "bad row strides / pair offsets", &empty); rc || empty) return rc;
     if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_split: head dim must be 16, 32, 64 or 128");
     if (const int rc = generic_launch_ok(ld_qkv, max_len, QT, B, seq_order, "attn_split")) return rc;
     AttnSplitArgs sa{{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H, softmax_scale * 1.4426950408889634f, 1, H * B,
@@ -2115,12 +1701,10 @@ extern "C" int esme_hip_attn_varlen_fwd_qkpair_f16_opts(const void* q, const voi
                                                         int max_len, float softmax_scale, const esme_attn_opts_t* opts, void* stream) {
     ESME_CHECK_ARG(!opts || opts->struct_bytes == (int)sizeof(esme_attn_opts_t), "attn_qkpair: options struct of another ABI");
     const int32_t* seq_order = opts ? opts->seq_order : nullptr;
-    ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0, "attn_qkpair: bad sizes");
-    if (T == 0 || B == 0) return ESME_OK;
-    ESME_CHECK_ARG(q && k && v && o && cu_lens, "attn_qkpair: null pointer");
-    ESME_CHECK_ARG(ld_qkv % 8 == 0 && lo_qk % 8 == 0 && lo_qk > 0 && ld_o % 4 == 0 && ld_o >= (int64_t)H * d, "attn_qkpair: bad row strides / pair offset");
-    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && (reinterpret_cast<uintptr_t>(o) & 7u) == 0, "attn_qkpair: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535, "attn_qkpair: max_len must be > 0, H <= 65535");
+    bool empty;
+    if (const int rc = attn_entry_checks("attn_qkpair", q, k, v, o, cu_lens, B, T, H, d, max_len,
+                                         ld_qkv % 8 == 0 && lo_qk % 8 == 0 && lo_qk > 0 && ld_o % 4 == 0 && ld_o >= (int64_t)H * d,
+                                         "bad row strides / pair offset", &empty); rc || empty) return rc;
     AttnSplitArgs sa{{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H, softmax_scale * 1.4426950408889634f, 1, H * B,
                       0.0f, 0, seq_order}, lo_qk, 0};
     const hipStream_t s = (hipStream_t)stream;

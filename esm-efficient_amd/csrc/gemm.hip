@@ -25,20 +25,14 @@
 // M/N edges: loads clamp the row index (re-reading a valid row), stores are guarded; the
 // only shape requirement is K % 64 == 0.
 #include "gemm.h"
-#ifndef ESME_GELU_PACKED
-#define ESME_GELU_PACKED 1
-#endif
 #include <atomic>
 #include <cstdlib>
 
-#ifndef ESME_GEMM_P3N
-#define ESME_GEMM_P3N 4            // eighths of a K-tile's LDS-DMA pieces issued two sub-steps early (sub-step 3 of the previous tile)
-#endif
-#ifndef ESME_GEMM_PERSIST_ROT
-#define ESME_GEMM_PERSIST_ROT 0
-#endif
-
 namespace esme {
+
+static constexpr int kGemmP3N = 4;            // eighths of a K-tile's LDS-DMA pieces issued two sub-steps early (sub-step 3 of the previous tile)
+// the 256 MB memory-side cache (Infinity Cache): smaller results are worth keeping there for the next kernel
+static constexpr int kNtMinMB = 256;
 
 template <int BM, int BN, int WM, int WN, int EPI, int ROTD = 0, bool LNF = false, bool STATS = false, bool PERSIST = false, bool R32 = false, bool PAIR = false, bool F16 = false, bool RP = false>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(const GemmArgs a) {
@@ -473,7 +467,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(const GemmArgs 
     // in the burst at the same time (tools/lab/dma_role_probe.hip).
     // Pieces [0, P3) of a K-tile are issued during sub-step 3 of the iteration TWO tiles earlier (right after the barrier
     // that frees their buffer), [P3, NP) during sub-step 0 of the previous iteration.
-    constexpr int P3 = (NP * ESME_GEMM_P3N) / 8;
+    constexpr int P3 = (NP * kGemmP3N) / 8;
     static_assert(FMH >= 2, "activation reads need FMH - 1 of every FMH MFMA slots");
     using std::integral_constant;
     auto sub = [&](FragW& w, const FragA& ca, auto H, auto NEWW, FragA& na, const char* nbase, const int nks,
@@ -948,13 +942,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(const GemmArgs 
                         else o[e] = acc[i][j][e];                       // bias already inside (rotary section / folded LayerNorm's c2)
                     }
                     if constexpr (EPI == ESME_EPI_GELU) {
-#if ESME_GELU_PACKED
                         const f32x2_t g0 = gelu_erf2<GELU_DEG>(f32x2_t{o[0], o[1]}), g1 = gelu_erf2<GELU_DEG>(f32x2_t{o[2], o[3]});
                         o[0] = g0[0]; o[1] = g0[1]; o[2] = g1[0]; o[3] = g1[1];
-#else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = gelu_erf<GELU_DEG>(o[e]);
-#endif
                     }
                     if constexpr (R32) {
                         const int n = nw0 + cl;
@@ -1181,7 +1170,7 @@ static int launch_one(GemmArgs& a, hipStream_t s) {
     set_raster<BM, BN>(a);
     int64_t blocks = (int64_t)a.tiles_m * a.tiles_n;
     if (blocks > 0x7fffffffLL) return fail(ESME_ERR_UNSUPPORTED, "gemm: grid too large");
-    if constexpr (!PERSIST && !PAIR && !RP && BM == 256 && BN == 256 && (ROTD == 0 || ESME_GEMM_PERSIST_ROT)) {     // (fused rotary: the epilogue's tables + the address set-up spill)
+    if constexpr (!PERSIST && !PAIR && !RP && BM == 256 && BN == 256 && ROTD == 0) {     // (fused rotary: the epilogue's tables + the address set-up spill)
         // Big tiles run one workgroup per CU (128 KB of LDS): once a launch is several rounds long, ONE persistent
         // workgroup per CU walks the tiles instead, fetching the next tile's first K-tile under the current epilogue.
         const int ncu = cu_count() & ~7;
@@ -1199,14 +1188,7 @@ static int launch_one(GemmArgs& a, hipStream_t s) {
     if (smem >= 64 * 1024) {
         // the attribute is per (kernel, device): one bit per device ordinal, set once, safe from any host thread
         static std::atomic<unsigned long long> done{0ull};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(done.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-                return fail(ESME_ERR_LAUNCH, "gemm: cannot raise the dynamic LDS limit");
-            done.fetch_or(bit, std::memory_order_release);
-        }
+        if (const int rc = raise_dynamic_lds(done, kern, smem, "gemm")) return rc;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned int)blocks), dim3(WM * WN * 64), smem, s, a);
     return check_launch("gemm_bf16");
@@ -1455,12 +1437,9 @@ extern "C" int esme_hip_gemm_bf16_opts(const void* A, int64_t lda, const void* W
     }
     const hipStream_t s = (hipStream_t)stream;
     a.stat_ld = M;
-#ifndef ESME_NT_MIN_MB
-#define ESME_NT_MIN_MB 256          // the 256 MB memory-side cache (Infinity Cache): smaller results are worth keeping there for the next kernel
-#endif
     {   // bytes this launch writes: C (16-bit) [+ its lo half] [+ the fp32 stream]
         const double out_bytes = (double)M * n_out * 2.0 * (a.pair_off ? 2.0 : 1.0) + (a.resid32 ? (double)M * N * 4.0 : 0.0);
-        a.stream_out = out_bytes > ESME_NT_MIN_MB * 1048576.0;
+        a.stream_out = out_bytes > kNtMinMB * 1048576.0;
     }
     const int tile = pick_tile(M, N, opts);
     if (tile == 1) return launch_gemm<128, 128, 2, 2>(a, epilogue, rotd, lnf, stats, s);

@@ -867,17 +867,11 @@ extern "C" int esme_hip_layernorm(const void* x, int64_t ldx, const void* w, con
     ESME_CHECK_ARG(aligned16(x) && aligned16(y) && aligned16(w) && (!b || aligned16(b)), "layernorm: misaligned");
     const dim3 grid((unsigned int)((T + 3) / 4)), block(256);
     const hipStream_t s = (hipStream_t)stream;
-#define ESME_LN(N)                                                                                            \
-    hipLaunchKernelGGL(layernorm_kernel<N>, grid, block, 0, s, (const u16*)x, ldx, (const u16*)w, (const u16*)b, \
-                       (u16*)y, ldy, T, E, eps)
-    if (E <= 512) ESME_LN(1);
-    else if (E <= 1024) ESME_LN(2);
-    else if (E <= 1536) ESME_LN(3);
-    else if (E <= 2560) ESME_LN(5);
-    else if (E <= 5120) ESME_LN(10);
-    else ESME_FAIL(ESME_ERR_UNSUPPORTED, "layernorm: E > 5120 unsupported");
-#undef ESME_LN
-    return check_launch("layernorm");
+    return dispatch_row_chunks(E, "layernorm", [&](auto nch) {
+        hipLaunchKernelGGL(layernorm_kernel<decltype(nch)::value>, grid, block, 0, s, (const u16*)x, ldx, (const u16*)w, (const u16*)b,
+                           (u16*)y, ldy, T, E, eps);
+        return check_launch("layernorm");
+    });
 }
 
 
@@ -892,16 +886,11 @@ extern "C" int esme_hip_residual_f32(float* x32, int64_t ld32, const void* o, in
                    "residual_f32: misaligned");
     const dim3 grid((unsigned int)((T + 3) / 4)), block(256);
     const hipStream_t s = (hipStream_t)stream;
-#define ESME_RF(N) hipLaunchKernelGGL(residual_f32_kernel<N>, grid, block, 0, s, x32, ld32, (const u16*)o, ldo, alpha, init, \
-                                      (u16*)x16, ld16, (f32x2*)sums, T, E)
-    if (E <= 512) ESME_RF(1);
-    else if (E <= 1024) ESME_RF(2);
-    else if (E <= 1536) ESME_RF(3);
-    else if (E <= 2560) ESME_RF(5);
-    else if (E <= 5120) ESME_RF(10);
-    else ESME_FAIL(ESME_ERR_UNSUPPORTED, "residual_f32: E > 5120 unsupported");
-#undef ESME_RF
-    return check_launch("residual_f32");
+    return dispatch_row_chunks(E, "residual_f32", [&](auto nch) {
+        hipLaunchKernelGGL(residual_f32_kernel<decltype(nch)::value>, grid, block, 0, s, x32, ld32, (const u16*)o, ldo, alpha, init,
+                           (u16*)x16, ld16, (f32x2*)sums, T, E);
+        return check_launch("residual_f32");
+    });
 }
 
 extern "C" int esme_hip_stream_operand_guarded(const float* x32, int64_t ld32, void* x16, int64_t ld16, int64_t lo_off, int f16, const float* scale,
@@ -919,16 +908,14 @@ extern "C" int esme_hip_stream_operand_guarded(const float* x32, int64_t ld32, v
                    "stream_operand: the extension tile is 64 columns between hi and lo (E <= ext_off, ext_off + 64 <= lo_off) with <= 64 selected channels");
     const dim3 grid((unsigned int)((T + 3) / 4)), block(256);
     const hipStream_t s = (hipStream_t)stream;
-#define ESME_SO(N) do { if (f16) hipLaunchKernelGGL((stream_operand_kernel<N, true>), grid, block, 0, s, x32, ld32, (u16*)x16, ld16, lo_off, scale, ext_sel, ext_n, ext_off, (f32x2*)sums, col_absmax, T, E); \
-                        else hipLaunchKernelGGL((stream_operand_kernel<N, false>), grid, block, 0, s, x32, ld32, (u16*)x16, ld16, lo_off, scale, ext_sel, ext_n, ext_off, (f32x2*)sums, col_absmax, T, E); } while (0)
-    if (E <= 512) ESME_SO(1);
-    else if (E <= 1024) ESME_SO(2);
-    else if (E <= 1536) ESME_SO(3);
-    else if (E <= 2560) ESME_SO(5);
-    else if (E <= 5120) ESME_SO(10);
-    else ESME_FAIL(ESME_ERR_UNSUPPORTED, "stream_operand: E > 5120 unsupported");
-#undef ESME_SO
-    return check_launch("stream_operand");
+    return dispatch_row_chunks(E, "stream_operand", [&](auto nch) {
+        constexpr int N = decltype(nch)::value;
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, grid, block, 0, s, x32, ld32, (u16*)x16, ld16, lo_off, scale, ext_sel, ext_n, ext_off, (f32x2*)sums, col_absmax, T, E);
+            return check_launch("stream_operand");
+        };
+        return f16 ? launch(stream_operand_kernel<N, true>) : launch(stream_operand_kernel<N, false>);
+    });
 }
 
 extern "C" int esme_hip_stream_operand_scaled(const float* x32, int64_t ld32, void* x16, int64_t ld16, int64_t lo_off, int f16, const float* scale,
@@ -963,15 +950,10 @@ extern "C" int esme_hip_layernorm_f32(const float* x, int64_t ldx, const void* w
     ESME_CHECK_ARG(aligned16(x) && aligned16(y) && aligned16(w) && (!b || aligned16(b)), "layernorm_f32: misaligned");
     const dim3 grid((unsigned int)((T + 3) / 4)), block(256);
     const hipStream_t s = (hipStream_t)stream;
-#define ESME_LNF(N) hipLaunchKernelGGL(layernorm_f32_kernel<N>, grid, block, 0, s, x, ldx, (const u16*)w, (const u16*)b, (u16*)y, ldy, T, E, eps)
-    if (E <= 512) ESME_LNF(1);
-    else if (E <= 1024) ESME_LNF(2);
-    else if (E <= 1536) ESME_LNF(3);
-    else if (E <= 2560) ESME_LNF(5);
-    else if (E <= 5120) ESME_LNF(10);
-    else ESME_FAIL(ESME_ERR_UNSUPPORTED, "layernorm_f32: E > 5120 unsupported");
-#undef ESME_LNF
-    return check_launch("layernorm_f32");
+    return dispatch_row_chunks(E, "layernorm_f32", [&](auto nch) {
+        hipLaunchKernelGGL(layernorm_f32_kernel<decltype(nch)::value>, grid, block, 0, s, x, ldx, (const u16*)w, (const u16*)b, (u16*)y, ldy, T, E, eps);
+        return check_launch("layernorm_f32");
+    });
 }
 
 extern "C" int esme_hip_layernorm_split_checked(const void* x, int64_t ldx, int in_pair, int64_t in_off, const void* w, const void* b, void* y,
@@ -987,17 +969,16 @@ extern "C" int esme_hip_layernorm_split_checked(const void* x, int64_t ldx, int 
                    "layernorm_split: misaligned");
     const dim3 grid((unsigned int)((T + 3) / 4)), block(256);
     const hipStream_t s = (hipStream_t)stream;
-#define ESME_LNS(N) do { if (in_pair == 2) hipLaunchKernelGGL((layernorm_split_kernel<N, 2>), grid, block, 0, s, x, ldx, in_off, (const u16*)w, (const u16*)b, (u16*)y, ldy, out_off, y32, ld32, T, E, eps, overflow_flag); \
-                         else if (in_pair) hipLaunchKernelGGL((layernorm_split_kernel<N, 1>), grid, block, 0, s, x, ldx, in_off, (const u16*)w, (const u16*)b, (u16*)y, ldy, out_off, y32, ld32, T, E, eps, overflow_flag); \
-                         else hipLaunchKernelGGL((layernorm_split_kernel<N, 0>), grid, block, 0, s, x, ldx, in_off, (const u16*)w, (const u16*)b, (u16*)y, ldy, out_off, y32, ld32, T, E, eps, overflow_flag); } while (0)
-    if (E <= 512) ESME_LNS(1);
-    else if (E <= 1024) ESME_LNS(2);
-    else if (E <= 1536) ESME_LNS(3);
-    else if (E <= 2560) ESME_LNS(5);
-    else if (E <= 5120) ESME_LNS(10);
-    else ESME_FAIL(ESME_ERR_UNSUPPORTED, "layernorm_split: E > 5120 unsupported");
-#undef ESME_LNS
-    return check_launch("layernorm_split");
+    return dispatch_row_chunks(E, "layernorm_split", [&](auto nch) {
+        constexpr int N = decltype(nch)::value;
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, grid, block, 0, s, x, ldx, in_off, (const u16*)w, (const u16*)b, (u16*)y, ldy, out_off, y32, ld32, T, E, eps, overflow_flag);
+            return check_launch("layernorm_split");
+        };
+        if (in_pair == 2) return launch(layernorm_split_kernel<N, 2>);
+        if (in_pair) return launch(layernorm_split_kernel<N, 1>);
+        return launch(layernorm_split_kernel<N, 0>);
+    });
 }
 
 extern "C" int esme_hip_layernorm_split(const void* x, int64_t ldx, int in_pair, int64_t in_off, const void* w, const void* b, void* y,
@@ -1046,15 +1027,10 @@ extern "C" int esme_hip_row_sums(const void* x, int64_t ldx, int64_t T, int E, f
                    (reinterpret_cast<uintptr_t>(sums) & 7u) == 0, "row_sums: null/misaligned pointer or E, ldx not multiples of 8");
     const dim3 grid((unsigned int)((T + 3) / 4)), block(256);
     const hipStream_t s = (hipStream_t)stream;
-#define ESME_RS(N) hipLaunchKernelGGL(row_sums_kernel<N>, grid, block, 0, s, (const u16*)x, ldx, T, E, (f32x2*)sums)
-    if (E <= 512) ESME_RS(1);
-    else if (E <= 1024) ESME_RS(2);
-    else if (E <= 1536) ESME_RS(3);
-    else if (E <= 2560) ESME_RS(5);
-    else if (E <= 5120) ESME_RS(10);
-    else ESME_FAIL(ESME_ERR_UNSUPPORTED, "row_sums: E > 5120 unsupported");
-#undef ESME_RS
-    return check_launch("row_sums");
+    return dispatch_row_chunks(E, "row_sums", [&](auto nch) {
+        hipLaunchKernelGGL(row_sums_kernel<decltype(nch)::value>, grid, block, 0, s, (const u16*)x, ldx, T, E, (f32x2*)sums);
+        return check_launch("row_sums");
+    });
 }
 
 static int rotary_impl(void* q, void* k, int64_t ld, const void* cosT, const void* sinT,
@@ -1146,24 +1122,19 @@ static int qk_norm_rotary_impl(void* q, void* k, int64_t ld, const void* wq, con
     ESME_CHECK_ARG(ld % 8 == 0 && ld >= E, "qk_norm_rotary: bad row stride");
     ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(wq) && aligned16(wk) && (!bq || aligned16(bq)) &&
                    (!bk || aligned16(bk)) && aligned16(cosT) && aligned16(sinT), "qk_norm_rotary: misaligned");
-#ifndef ESME_QKN_RPW
-#define ESME_QKN_RPW 2
-#endif
-    constexpr int RPW = ESME_QKN_RPW;                        // rows per wave
+    constexpr int RPW = 2;                                   // rows per wave
     const dim3 grid((unsigned int)((T + 2 * RPW - 1) / (2 * RPW))), block(256);
     const hipStream_t s = (hipStream_t)stream;
-#define ESME_QKN(N)                                                                                                 \
-    do { if (f16) hipLaunchKernelGGL((qk_norm_rotary_kernel<N, RPW, true>), grid, block, 0, s, (u16*)q, (u16*)k, ld, (const u16*)wq, (const u16*)wk, \
-                       (const u16*)bq, (const u16*)bk, eps, (const u16*)cosT, (const u16*)sinT, pos, T, E, head_dim, max_len, q_scale, qk_sumsq); \
-    else hipLaunchKernelGGL((qk_norm_rotary_kernel<N, RPW>), grid, block, 0, s, (u16*)q, (u16*)k, ld, (const u16*)wq, (const u16*)wk, \
-                       (const u16*)bq, (const u16*)bk, eps, (const u16*)cosT, (const u16*)sinT, pos, T, E, head_dim, max_len, q_scale, (unsigned int*)nullptr); } while (0)
-    if (E <= 512) ESME_QKN(1);
-    else if (E <= 1024) ESME_QKN(2);
-    else if (E <= 1536) ESME_QKN(3);
-    else if (E <= 2560) ESME_QKN(5);
-    else ESME_QKN(10);
-#undef ESME_QKN
-    return check_launch("qk_norm_rotary");
+    // (E > 5120 was refused above with this entry's own text: the dispatcher's failing arm is not reached)
+    return dispatch_row_chunks(E, "qk_norm_rotary", [&](auto nch) {
+        constexpr int N = decltype(nch)::value;
+        auto launch = [&](auto kern, unsigned int* sumsq) {
+            hipLaunchKernelGGL(kern, grid, block, 0, s, (u16*)q, (u16*)k, ld, (const u16*)wq, (const u16*)wk, (const u16*)bq, (const u16*)bk, eps,
+                               (const u16*)cosT, (const u16*)sinT, pos, T, E, head_dim, max_len, q_scale, sumsq);
+            return check_launch("qk_norm_rotary");
+        };
+        return f16 ? launch(qk_norm_rotary_kernel<N, RPW, true>, qk_sumsq) : launch(qk_norm_rotary_kernel<N, RPW>, nullptr);
+    });
 }
 
 extern "C" int esme_hip_qk_norm_rotary_scaled(void* q, void* k, int64_t ld, const void* wq, const void* wk, const void* bq,

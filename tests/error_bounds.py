@@ -144,7 +144,7 @@ def gelu_prime64(y):
 
 
 def gelu_bound(y, pre, deg):
-    """GELU epilogue (gemm.hip:952-956, common.h:186-193): the input error through |gelu'| (|gelu''| <= 0.8 covers its change over
+    """GELU epilogue (gemm.hip:945-946 in gemm_bf16_kernel, common.h:175-182 above gelu_poly): the input error through |gelu'| (|gelu''| <= 0.8 covers its change over
     the interval), plus the polynomial's stated error: 0.19 (degree 5) or 0.002 (degree 7) of half a bf16 ulp of the result, floor
     1.5e-7 |x|; plus the fma that forms max(x, 0) - |x| 2^p (one fp32 rounding)."""
     g = gelu64(y)
@@ -160,23 +160,23 @@ def gemm_reference(a, w, bias=None, epi='none', resid=None, alpha=1.0, out_fmt='
     pre = dot_term(a64, w64, k_eff)
     if bias is not None:
         y = y + bias.double()
-        pre = pre + U32 * y.abs()                           # acc + bias, one fp32 add (gemm.hip:947)
+        pre = pre + U32 * y.abs()                           # acc + bias, one fp32 add (gemm.hip:941, gemm_bf16_kernel)
     if epi == 'none':
         val = y
     elif epi == 'gelu':
         val = gelu64(y)
-        pre = gelu_bound(y, pre, gelu_deg)                  # gemm.hip:952-956
+        pre = gelu_bound(y, pre, gelu_deg)                  # gemm.hip:945-946, gemm_bf16_kernel
     elif epi == 'residual':
         r = resid.double()
         val = r + alpha * y
-        pre = abs(alpha) * pre + U32 * (abs(alpha) * y.abs() + val.abs())     # bf(r) + alpha * o: mul and add (gemm.hip:967-968)
+        pre = abs(alpha) * pre + U32 * (abs(alpha) * y.abs() + val.abs())     # bf(r) + alpha * o: mul and add (gemm.hip:956-957, gemm_bf16_kernel)
     else:
         raise ValueError(epi)
-    return val, pre + out_round(val, pre, out_fmt, pair), pre  # pack16 / the pair split: one rounding each (gemm.hip:971-974)
+    return val, pre + out_round(val, pre, out_fmt, pair), pre  # pack16 / the pair split: one rounding each (gemm.hip:960-963, gemm_bf16_kernel)
 
 
 def swiglu_reference(a, wa, wf, out_fmt='bf16'):
-    """SwiGLU epilogue (gemm.hip:942): gate * rcp(1 + exp2(-log2(e) gate)) * fc.  Steps: the exp2 argument's fp32 product
+    """SwiGLU epilogue (gemm.hip:936, gemm_bf16_kernel): gate * rcp(1 + exp2(-log2(e) gate)) * fc.  Steps: the exp2 argument's fp32 product
     (relative ln2 * 2^-24 |log2(e) gate| = 2^-24 |gate| on the exponential), v_exp_f32, the add of 1, v_rcp_f32, two products.  The
     input errors propagate through |d silu / d gate| <= 1.1 and |silu(gate)|."""
     a64 = a.double()
@@ -193,9 +193,9 @@ def swiglu_reference(a, wa, wf, out_fmt='bf16'):
 def ln_fold_reference(x, wprime, c1, c2, eps, sums=None, dim=None):
     """LayerNorm fold: y = rstd (acc - mean c1) + c2 with acc = x . W'[n], computed from the operands handed to the kernel -- x (the MFMA
     operand), W', c1, c2 and the fp32 partial sums {sum, sum of squares} (`sums`, (T, 2) or (nblk, T, 2); None: exact sums of x).
-    Steps (gemm.hip:339-343): mean = s1 * fl(1/E) (two roundings), var = s2 * fl(1/E) - mean^2 (two products, one subtraction: the
+    Steps (gemm.hip:333-337, gemm_bf16_kernel): mean = s1 * fl(1/E) (two roundings), var = s2 * fl(1/E) - mean^2 (two products, one subtraction: the
     cancellation term 2^-24 (s2/E + mean^2), large against var when |mean| >> std -- the dc20 / outlier kinds), rstd = v_rsq_f32 of
-    var + eps (one add, E_TRANS), rstd * mean (one product); the epilogue (gemm.hip:588) fma(rstd, acc, fma(-rstd mean, c1, c2)): two
+    var + eps (one add, E_TRANS), rstd * mean (one product); the epilogue (gemm.hip:582, gemm_bf16_kernel) fma(rstd, acc, fma(-rstd mean, c1, c2)): two
     roundings, 2^-24 (|c2 - rstd mean c1| + |y|).  The accumulation term enters scaled by rstd."""
     x64 = x.double()
     E = x64.shape[1] if dim is None else dim
@@ -230,8 +230,8 @@ def rotary_apply64(x, cos, sin, pos):
 
 
 def rotary_bound(x, pre, cos, sin, pos, q_scale=None):
-    """Rotation in fp32 with the tables in their stated type (gemm.hip:667-668, rowops.hip:353-393): one product rounded,
-    one fused -- 2^-24 (|lo c| + |up s|) + 2^-24 |result|; the input error `pre` enters through |c| + |s| <= sqrt 2; q_scale (gemm.hip:683)
+    """Rotation in fp32 with the tables in their stated type (gemm.hip:661-662 in gemm_bf16_kernel, rowops.hip:353-386 rotary_kernel): one product rounded,
+    one fused -- 2^-24 (|lo c| + |up s|) + 2^-24 |result|; the input error `pre` enters through |c| + |s| <= sqrt 2; q_scale (gemm.hip:677, gemm_bf16_kernel)
     rounds once more."""
     d = x.shape[-1]
     c = cos.double()[pos.long(), : d // 2].unsqueeze(1)
@@ -255,7 +255,7 @@ def rotary_bound(x, pre, cos, sin, pos, q_scale=None):
 P_UNIT = {'bf16': 2.0 ** -8, 'fp16': 2.0 ** -11, 'fp32': 2.0 ** -24, 'bf16pair': 2.0 ** -16 + 2.0 ** -16}
 
 
-# query rows per work item of the fixed-reference fp16 form (attn_pp64_kernel<4, true, D, true>: ROWS = NW * 64, attn.hip:695)
+# query rows per work item of the fixed-reference fp16 form (attn_pp64_kernel<4, true, D, true>: ROWS = NW * 64, attn.hip:687)
 FIXED_REF_ITEM_ROWS = 256
 
 
@@ -266,23 +266,27 @@ def attention_reference(q, k, v, cu_lens, heads, scale, p_fmt, out_fmt, log2_uni
         u_P (C_DOT ||p o v||_2 + |o|) + (2 e_exp + 2 e_score) * sum_j p_j |v_j| + subnormal floor of P + PV accumulation + 1/l and product
         + 1/2 ulp(o)
 
-    - u_P: P rounded to its format before the PV MFMA (attn.hip:1695 pack_bf16 and its fp16 / pair forms): relative half an ulp per
-      term.  The row sum l adds the UNROUNDED P (attn.hip:1696, pair_sum_pack; only the ESME_ATTN_ABL & 2 lab ablation, which gives
-      wrong results by design, sums the rounded P by MFMA), so these roundings enter the numerator only: C_DOT u_P ||p o v||_2 for
+    - u_P: P rounded to its format before the PV MFMA (attn.hip:870 pack16 in attn_pp64_kernel's pair_sum_pack, :1292 in
+      attn_sb_kernel's, and the fp16 / pair forms): relative half an ulp per
+      term.  The row sum l adds the UNROUNDED P (attn.hip:871, pair_sum_pack in attn_pp64_kernel; :1293 in attn_sb_kernel: no kernel
+      in the library sums the rounded P), so these roundings enter the numerator only: C_DOT u_P ||p o v||_2 for
       the independent part (keys with distinct scores round independently), plus u_P |o| for the part they share (a row whose keys
       tie rounds every P alike: its error is u_P o).  Sized by test_error_bounds_cpu.py::test_c_dot_covers_p_rounding.  The worst case
       u_P sum_j p_j |v_j| would accept a bf16 P or a bf16 output in one fp16 work item of a 700-key sequence;
-    - e_exp: v_exp_f32 (attn.hip:279, :557, :900-909), plus the fp32 fma that forms its argument score * c - m (2^-24 of |argument|)
+    - e_exp: v_exp_f32 (attn.hip:271 attn_varlen_kernel, :549 attn_split_kernel, :877-886 softmax_slot in attn_pp64_kernel),
+      plus the fp32 fma that forms its argument score * c - m (2^-24 of |argument|)
       and the subtraction's own rounding;
     - e_score: fp32 accumulation of the score products (C_DOT form over d), times scale * log2(e), in log2 units -> ln 2 relative;
       the row sum and the output then see each perturbation twice (numerator and normaliser), hence the factors 2;
     - fp16 P below 2^-14 (subnormal): absolute 2^-25 per term, relative to the kernel's row sum l = sum 2^(t_j - r), r the reference
       the kernel subtracts.  Forms with a maximum: r = the row maximum (a first-tile reference is lower and only makes l larger).  The
       fixed-reference form (fixed_ref = 4, q_prescaled fp16): r = 4, unless the item_rows-row work item is redone with exact maxima
-      -- the kernel's own test (attn.hip:1099-1105): a row whose sum at reference 4 falls below S * 2^-14 (S = the sequence length)
+      -- the kernel's own test (attn.hip:1069-1076, attn_pp64_kernel): a row whose sum at reference 4 falls below S * 2^-14
+      (S = the sequence length)
       redoes its whole work item.  Items with a row clearly under that threshold (half of it) take r = the row maximum; every other
       row r = max(4, row maximum), the larger of the two bounds (an item redone for overflow subtracts its maximum, above 4);
-    - 1 / l then o * inv (attn.hip:1861-1868): E_TRANS + 2^-24 relative; the output rounding half an ulp (pair: of the pair).
+    - 1 / l then o * inv (attn.hip:1093-1100, attn_pp64_kernel; :314-324 attn_varlen_kernel): E_TRANS + 2^-24 relative; the
+      output rounding half an ulp (pair: of the pair).
     q / k / v: (T, H*d), for a pair the sum hi + lo; qk_drop (q / k as pairs): the relative size of the Ql Kl product the pair
     kernels leave out (bf16 pairs 2^-16, fp16 pairs 2^-22), times sum |q k|, with three accumulation passes instead of one."""
     T, E = q.shape
@@ -335,7 +339,7 @@ def attention_reference(q, k, v, cu_lens, heads, scale, p_fmt, out_fmt, log2_uni
 # ------------------------------------------------------------------ recipes: row ops
 
 def layernorm_reference(x, w, b, eps, out_fmt, pair=False):
-    """esme_hip_layernorm* (rowops.hip:103-145): mean = fp32 sum * (1/E), var = fp32 sum of (x - mean)^2 * (1/E), rstd = v_rsq_f32,
+    """esme_hip_layernorm* (rowops.hip:103-145, layernorm_kernel): mean = fp32 sum * (1/E), var = fp32 sum of (x - mean)^2 * (1/E), rstd = v_rsq_f32,
     y = fma((x - mean) * rstd, w, b) -- per element  |w| rstd (|x - mean| e_rel + dmean) + 2^-24 (|(x - mean) rstd w| + |y|), with
     e_rel = 1/2 dvar / var + E_TRANS (rsq) + 2^-24 (x - mean) + 2^-24 (the product with rstd); then the output rounding."""
     x64 = x.double()
@@ -356,7 +360,7 @@ def layernorm_reference(x, w, b, eps, out_fmt, pair=False):
 
 
 def softmax_reference(x, log, out_fmt):
-    """esme_hip_softmax_rows* (rowops.hip:729-753): m = max, e = __expf(v - m) (v_exp_f32 of (v - m) log2 e: 2^-24 |v - m| on the
+    """esme_hip_softmax_rows* (rowops.hip:729-753, softmax_rows_kernel and softmax_rows_f32_kernel): m = max, e = __expf(v - m) (v_exp_f32 of (v - m) log2 e: 2^-24 |v - m| on the
     argument, E_TRANS), sum in fp32 over V <= 64 terms (V 2^-24 relative), then e / sum or (v - m) - __logf(sum)."""
     x64 = x.double()
     V = x64.shape[1]

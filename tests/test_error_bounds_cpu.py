@@ -200,7 +200,7 @@ def _f32(x):
 
 @pytest.mark.parametrize('kind', ['plain', 'dc20', 'outlier'])
 def test_ln_fold_recipe_accepts_the_kernels_fp32_arithmetic(kind):
-    """gemm.hip:339-343 and :588 emulated step by step in fp32 (fma as the float64 value of the exact product-sum, rounded once)."""
+    """gemm.hip:333-337 and :582 (gemm_bf16_kernel: the LN-fold row statistics and its epilogue fma) emulated step by step in fp32 (fma as the float64 value of the exact product-sum, rounded once)."""
     T, E, N = 300, 640, 256
     g = torch.Generator().manual_seed(len(kind))
     x = torch.randn(T, E, generator=g) * 1.5
@@ -401,7 +401,7 @@ def test_c_dot_covers_p_rounding(p_fmt, p_dtype):
 
 def emulate_fixed_reference(qs, k, v, cu, H, redo=True, item_rows=eb.FIXED_REF_ITEM_ROWS):
     """The fixed-reference fp16 form: t = qs . k in fp32 (log2 units), P = fp16(2^(t - 4)), l the fp32 sum of the unrounded P; a work item with a
-    row whose l falls below S * 2^-14 is redone with P = fp16(2^(t - row max)) (attn.hip:1099-1105).  redo = False: the defect, no redo."""
+    row whose l falls below S * 2^-14 is redone with P = fp16(2^(t - row max)) (attn.hip:1069-1076, attn_pp64_kernel).  redo = False: the defect, no redo."""
     T, E = qs.shape
     d = E // H
     out = torch.empty(T, E, dtype=torch.float32)

@@ -134,7 +134,7 @@ def test_gemm_layernorm_fold(kind, tile, persist):
     record('gemm LN fold', eb.assert_bounded(got, y, pre + eb.out_round(y, pre, 'bf16'), f'LN fold {kind} tile{tile} persist{persist}',
                                              eb.gemm_layout(128 * tile, 128 * tile)), eb.budget_used(got, y, pre + eb.out_round(y, pre, 'bf16'), pre))
     record_bias('gemm LN fold', got, y, pre, 'bf16')
-    gp = eb.gelu_bound(y, pre, 5)                                      # the LN-folded site runs the degree-5 polynomial (gemm.hip:901)
+    gp = eb.gelu_bound(y, pre, 5)                                      # the LN-folded site runs the degree-5 polynomial (gemm.hip:895, gemm_bf16_kernel)
     gv = eb.gelu64(y)
     record('gemm LN fold + gelu', eb.assert_bounded(gel, gv, gp + eb.out_round(gv, gp, 'bf16'), f'LN fold gelu {kind}'))
 
@@ -191,7 +191,7 @@ def test_gemm_residual_stats_and_fp32_stream(M, N, K, tile, persist):
     sb = torch.stack((eb.C_DOT * eb.U32 * math.sqrt(N) * torch.sqrt((o * o).sum(1)) + nblk * eb.U32 * o.abs().sum(1),
                       eb.C_DOT * eb.U32 * math.sqrt(N) * torch.sqrt((o ** 4).sum(1)) + (nblk + 1) * eb.U32 * (o * o).sum(1)), 1)
     record('gemm stats_out', eb.assert_bounded(st, s_ref, sb, 'stats_out'))
-    # fp32 residual stream: x32 <- fma(alpha, acc + bias, x32) (gemm.hip:963), one rounding; x16 = its bf16 rounding, bit for bit
+    # fp32 residual stream: x32 <- fma(alpha, acc + bias, x32) (gemm.hip:952, gemm_bf16_kernel), one rounding; x16 = its bf16 rounding, bit for bit
     y, _, pre = eb.gemm_reference(a, w, b)
     ref32 = x32.double() + 0.5 * y
     pre32 = 0.5 * pre + eb.U32 * ref32.abs()
@@ -229,7 +229,7 @@ def test_gemm_f16(M, N, K, tile, persist):
     gv = eb.gelu64(ref)
     gp = eb.gelu_bound(ref, pre, 7)
     record('gemm fp16 gelu', eb.assert_bounded(gel, gv, gp + eb.out_round(gv, gp, 'fp16'), 'f16 gelu'))
-    # (gemm.hip:794-795): x * si one product, fma with alpha, then * so one product; the pair split of the stored value
+    # (gemm.hip:788-789, gemm_bf16_kernel): x * si one product, fma with alpha, then * so one product; the pair split of the stored value
     xn = xin + 0.7 * ref
     pre_x = eb.U32 * xin.abs() + 0.7 * pre + eb.U32 * xn.abs()
     st_ref = xn * so.double()
@@ -467,7 +467,7 @@ def test_attention_f16_redo_items(case):
     qs = (q.float() * (d ** -0.5 * LOG2E)).to(H16).to(DEV)
     k = k.to(DEV)
     got = _hip.attn_varlen(qs, k, v, cu, max(lengths), H, q_prescaled=True)
-    if case == 'vanished':              # the batch does what it is for: rows whose sum at reference 4 is far under S * 2^-14 (attn.hip:1099-1105)
+    if case == 'vanished':              # the batch does what it is for: rows whose sum at reference 4 is far under S * 2^-14 (attn.hip:1069-1076, attn_pp64_kernel)
         cl = cu.tolist()
         for s0, s1 in zip(cl[:-1], cl[1:]):
             t = qs[s0:s1].double().view(-1, H, d).transpose(0, 1) @ k[s0:s1].double().view(-1, H, d).permute(1, 2, 0)
@@ -662,7 +662,7 @@ def test_residual_f32_and_stream_operand(T, E):
         _hip.residual_f32_(xs, o, 0.37, x16, sums, init=init)
         ref = (0.0 if init else x32.double()) + float(np.float32(0.37)) * o.double()
         record('residual_f32', eb.assert_bounded(xs, ref, eb.half_ulp(ref, 'fp32'),
-                                                 f'residual_f32 init={init}'))      # alpha * o or fma: one rounding (rowops.hip:175, :179)
+                                                 f'residual_f32 init={init}'))      # alpha * o or fma: one rounding (rowops.hip:175, :179, residual_f32_kernel)
         assert torch.equal(x16, xs.to(BF))
         if xs.numel() >= BIAS_MIN_ELEMENTS:
             record_bias('residual_f32', xs, ref, torch.zeros_like(ref), 'fp32')

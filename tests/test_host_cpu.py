@@ -729,3 +729,31 @@ def test_misaligned_pointer_or_stride_is_refused_before_any_launch(name, args, b
         if code not in (-1, -2):
             missed.append(f'argument {i} = {v:#x}: code {code} ({_hip.load().esme_hip_last_error()})')
     assert not missed, f'{name}: not refused on the host: ' + '; '.join(missed)
+
+
+# ------------------------------------------------------------------ the row kernels keep a row in registers: widths above 5 120 are refused
+
+_E_WIDE = 5128        # the first multiple of 8 past the widest instantiation (10 chunks of 512 elements)
+
+
+def _too_wide_table():
+    """(entry point, message prefix, arguments that pass every other check with E = _E_WIDE)"""
+    P, E = _P, _E_WIDE
+    return [
+        ('esme_hip_layernorm', b'layernorm', [P, E, P, P, P, E, 4, E, 1e-5]),
+        ('esme_hip_residual_f32', b'residual_f32', [P, E, P, E, 0.5, 0, P, E, P, 4, E]),
+        ('esme_hip_stream_operand_guarded', b'stream_operand', [P, E, P, E, 0, 0, None, None, 0, 0, P, None, 4, E]),
+        ('esme_hip_layernorm_f32', b'layernorm_f32', [P, E, P, P, P, E, 4, E, 1e-5]),
+        ('esme_hip_layernorm_split_checked', b'layernorm_split', [P, 2 * E, 1, E, P, P, P, 2 * E, E, P, E, 4, E, 1e-5, None]),
+        ('esme_hip_row_sums', b'row_sums', [P, E, 4, E, P]),
+    ]
+
+
+@pytest.mark.parametrize('name,prefix,args', _too_wide_table(), ids=[t[0] for t in _too_wide_table()])
+def test_rows_wider_than_5120_are_unsupported_before_any_launch(name, prefix, args):
+    """Every entry point that picks its kernel by the row width E refuses E > 5 120 on the host with ESME_ERR_UNSUPPORTED and its own
+    '<entry>: E > 5120 unsupported' text (every other argument of these calls is valid, and nothing is launched)."""
+    from esme import _hip
+    lib = _hip.load()
+    assert getattr(lib, name)(*args, None) == -2
+    assert lib.esme_hip_last_error() == prefix + b': E > 5120 unsupported'
