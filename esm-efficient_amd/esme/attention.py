@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from esme import _hip
-from esme.nn import GELU, LayerNorm, Linear, weights_epoch
+from esme.nn import GELU, Derived, LayerNorm, Linear, weights_epoch
 from esme.rotary import RotaryEmbedding
 
 # head dim 64 / 32 with fused rotary: softmax_scale * log2(e) folded into q by the QKV epilogue, attention without a reference maximum
@@ -249,6 +249,22 @@ def _fold_layernorm_pow2(w: torch.Tensor, bias: Optional[torch.Tensor], gamma: t
     return wf, c1, c2.contiguous(), rho, (1.0 / rho).contiguous()
 
 
+def _build_fold(f16: bool, operands):
+    """operands() = (W, bias, gamma, beta) -> (W', c1, c2) in bfloat16, or with `f16` ((W', c1, c2), (rho, 1 / rho)) in float16 (precision
+    'half': _fold_layernorm_pow2; rho is the part of gamma that rides on the pair stream)."""
+    if f16:
+        *fold, rho, rho_inv = _fold_layernorm_pow2(*operands())
+        return tuple(fold), (rho, rho_inv)
+    return _fold_layernorm(*operands(), torch.bfloat16)
+
+
+def _to_f16(w: torch.Tensor) -> torch.Tensor:
+    """float16 copy of a bfloat16 weight (precision 'half'): exact for |w| >= 2^-14 (bf16 has 8 significant bits)."""
+    w16 = w.data.to(torch.float16).contiguous()
+    _check_fp16_range(w16)
+    return w16
+
+
 def _score_bound(q: torch.Tensor, k: torch.Tensor, heads: int, d: int, scale: float) -> torch.Tensor:
     """Upper bound of |softmax_scale * q_i . k_j| over all rows and heads (max row norm of q times max row norm of k per head): what the
     calibration forward of precision 'half' records per layer (a device scalar; no sync here)."""
@@ -288,92 +304,70 @@ class FlashMultiheadAttention(nn.Module):
         if pre_layernorm:
             self.layernorm_q = LayerNorm(embed_dim, bias=bias, dtype=dtype)
             self.layernorm_k = LayerNorm(embed_dim, bias=bias, dtype=dtype)
-        self._qkv_w: Optional[torch.Tensor] = None
-        self._qkv_b: Optional[torch.Tensor] = None
-        self._pack_key = None
-        self._fold = None           # (W', c1, c2) of the LN-folded QKV projection
-        self._fold_key = None
-        self._fold16 = None         # the same with W' = W * pow2(gamma) in float16 (precision 'half'), and the float16 out-projection weight
-        self._fold16_key = None
-        self._rho16 = None          # (rho, 1 / rho) float32 (phys_dim): the part of gamma that rides on the pair stream (_fold_layernorm_pow2)
-        self._fold16x = None        # (key, [W' | W'[:, sel] | 0]): the extension K-tile form (HalfPlan.ext_sel)
+        # derived weight copies: 'pack' (QKV weight, bias, padded out-projection weight, bias), 'fold' (W', c1, c2) of the LN-folded QKV projection,
+        # 'fold16' the same with W' = W * pow2(gamma) in float16 plus (rho, 1 / rho) (precision 'half'), 'fold16x' its extension K-tile form,
+        # 'out16' the float16 out-projection weight, 'lora' the adapter forms (_lora_weights)
+        self._derived = Derived()
         self.layer_index = 0        # position in the model's layer stack (set by the model; HalfPlan.pairs_at)
-        self._out16 = None
-        self._out16_key = None
         self._q4_qkv = None         # esme.quantization.Q4Matrix pair when the layer is 4-bit
         self._q4_out = None
-        self._out_w = self._out_b = None    # padded out-projection (padded layouts only)
         self._has_lora = False      # set by ESM2.add_lora: q / k / v / out may be esme.lora.LoRA wrappers
-        self._lora_cache = None     # (key, derived adapter weights): _lora_weights
 
     # -- weight layout ------------------------------------------------------
+    def _pack_key(self):
+        return _version_key(self.q.weight, self.k.weight, self.v.weight, self.q.bias, self.k.bias, self.v.bias,
+                            *((self.out.weight, self.out.bias) if self.padded else ()))
+
     def _pack(self):
         """Fuse q/k/v into one (3E, E) weight (+ (3E,) bias) and re-point the three
         parameters at row slices of it: state_dict() is unchanged, memory is not
-        duplicated, and the projection is a single N = 3E GEMM."""
-        key = _version_key(self.q.weight, self.k.weight, self.v.weight, self.q.bias, self.k.bias, self.v.bias,
-                           *((self.out.weight, self.out.bias) if self.padded else ()))
-        if key == self._pack_key:
-            return
-        E = self.embed_dim
+        duplicated, and the projection is a single N = 3E GEMM.  Returns (W_qkv, b_qkv, W_o, b_o);
+        the last two are the padded out-projection (padded layouts only, else None)."""
         if self.padded:
-            Ea, Ep = self.attn_dim, self.phys_dim
-            with torch.no_grad():
-                slots = head_slots(self.num_heads, self.head_dim, self.head_pad, self.q.weight.device)
-                w = torch.zeros(3 * Ea, Ep, dtype=self.q.weight.dtype, device=self.q.weight.device)
-                b = torch.zeros(3 * Ea, dtype=w.dtype, device=w.device) if self.q.bias is not None else None
-                for i, lin in enumerate((self.q, self.k, self.v)):
-                    w[i * Ea + slots, :E] = lin.weight.data
-                    if b is not None:
-                        b[i * Ea + slots] = lin.bias.data
-                self._qkv_w, self._qkv_b = w, b
-                ow = torch.zeros(Ep, Ea, dtype=w.dtype, device=w.device)
-                ow[:E, slots] = self.out.weight.data
-                self._out_w = ow
-                self._out_b = _pad_last(self.out.bias.data, Ep) if self.out.bias is not None else None
-            self._pack_key = key
-            return
-        with torch.no_grad():
-            w = torch.cat((self.q.weight.data, self.k.weight.data, self.v.weight.data), dim=0).contiguous()
-            for i, lin in enumerate((self.q, self.k, self.v)):
-                lin.weight.data = w[i * E:(i + 1) * E]
-            self._qkv_w = w
-            if self.q.bias is not None:
-                b = torch.cat((self.q.bias.data, self.k.bias.data, self.v.bias.data)).contiguous()
-                for i, lin in enumerate((self.q, self.k, self.v)):
-                    lin.bias.data = b[i * E:(i + 1) * E]
-                self._qkv_b = b
-            else:
-                self._qkv_b = None
-        self._pack_key = _version_key(self.q.weight, self.k.weight, self.v.weight,
-                                      self.q.bias, self.k.bias, self.v.bias)
+            return self._derived.get('pack', self._pack_key(), self._build_pack_padded)
+        return self._derived.get('pack', self._pack_key(), self._build_pack, rekey=self._pack_key)      # (the build moves q / k / v: the key of their new addresses)
+
+    def _build_pack(self):
+        E, lins = self.embed_dim, (self.q, self.k, self.v)
+        w = torch.cat([lin.weight.data for lin in lins], dim=0).contiguous()
+        b = torch.cat([lin.bias.data for lin in lins]).contiguous() if self.q.bias is not None else None
+        for i, lin in enumerate(lins):
+            lin.weight.data = w[i * E:(i + 1) * E]
+            if b is not None:
+                lin.bias.data = b[i * E:(i + 1) * E]
+        return w, b, None, None
+
+    def _build_pack_padded(self):
+        E, Ea, Ep = self.embed_dim, self.attn_dim, self.phys_dim
+        slots = head_slots(self.num_heads, self.head_dim, self.head_pad, self.q.weight.device)
+        w = torch.zeros(3 * Ea, Ep, dtype=self.q.weight.dtype, device=self.q.weight.device)
+        b = torch.zeros(3 * Ea, dtype=w.dtype, device=w.device) if self.q.bias is not None else None
+        for i, lin in enumerate((self.q, self.k, self.v)):
+            w[i * Ea + slots, :E] = lin.weight.data
+            if b is not None:
+                b[i * Ea + slots] = lin.bias.data
+        ow = torch.zeros(Ep, Ea, dtype=w.dtype, device=w.device)
+        ow[:E, slots] = self.out.weight.data
+        return w, b, ow, _pad_last(self.out.bias.data, Ep) if self.out.bias is not None else None
+
+    def _fold_operands(self):
+        w, b, _, _ = self._pack()
+        return (w, b, _pad_last(self.norm.weight.data, self.phys_dim),
+                _pad_last(self.norm.bias.data, self.phys_dim) if self.norm.bias is not None else None)
 
     def _pack_fold(self, f16: bool = False):
-        """LN-folded copy of the fused QKV weight (self.norm folded in); `f16`: W' in float16 (precision 'half')."""
+        """LN-folded copy of the fused QKV weight (self.norm folded in): (W', c1, c2); `f16`: ((W', c1, c2), (rho, 1 / rho)) with W' in
+        float16 (precision 'half')."""
         self._pack()
-        key = (self._pack_key, _version_key(self.norm.weight, self.norm.bias))
-        if key != (self._fold16_key if f16 else self._fold_key):
-            with torch.no_grad():
-                gamma = _pad_last(self.norm.weight.data, self.phys_dim)
-                beta = _pad_last(self.norm.bias.data, self.phys_dim) if self.norm.bias is not None else None
-                if f16:
-                    *fold, rho, rho_inv = _fold_layernorm_pow2(self._qkv_w, self._qkv_b, gamma, beta)
-                    fold, self._rho16 = tuple(fold), (rho, rho_inv)
-                else:
-                    fold = _fold_layernorm(self._qkv_w, self._qkv_b, gamma, beta, torch.bfloat16)
-            if f16:
-                self._fold16, self._fold16_key = fold, key
-            else:
-                self._fold, self._fold_key = fold, key
-        return self._fold16 if f16 else self._fold
+        return self._derived.get('fold16' if f16 else 'fold', (self._derived.key('pack'), _version_key(self.norm.weight, self.norm.bias)),
+                                 _build_fold, f16, self._fold_operands)
 
     def stream_scale(self):
         """precision 'half': (rho, 1 / rho) of this block's LayerNorm -- the per-column scaling the pair stream carries when the
         LayerNorm-folded QKV projection reads it."""
         if self._q4_qkv is not None:
             raise NotImplementedError("precision='half' runs the LayerNorm-folded path on unquantised weights")
-        self._pack_fold(True)
-        return self._rho16
+        return self._pack_fold(True)[1]
 
     def _weights_qkv(self, fold: bool, f16: bool = False, ext_sel: Optional[torch.Tensor] = None):
         """(W, bias, c1, c2) of the fused QKV projection: the LN-folded form when `fold`
@@ -382,13 +376,9 @@ class FlashMultiheadAttention(nn.Module):
         if f16:
             if self._q4_qkv is not None or not fold:
                 raise NotImplementedError("precision='half' runs the LayerNorm-folded path on unquantised weights")
-            wf, c1, c2 = self._pack_fold(True)
+            (wf, c1, c2), _ = self._pack_fold(True)
             if ext_sel is not None:
-                key = (self._fold16_key, _ext_key(ext_sel))       # (the channel LIST, not the tensor's address: ADVICE r5)
-                if self._fold16x is None or self._fold16x[0] != key:
-                    with torch.no_grad():
-                        self._fold16x = (key, _extend_k(wf, ext_sel))
-                wf = self._fold16x[1]
+                wf = self._derived.get('fold16x', (self._derived.key('fold16'), _ext_key(ext_sel)), _extend_k, wf, ext_sel)      # (keyed on the channel LIST, not the tensor's address: ADVICE r5)
             return wf, None, c1, c2
         if self._q4_qkv is not None:
             if fold:
@@ -398,26 +388,19 @@ class FlashMultiheadAttention(nn.Module):
         if fold:
             wf, c1, c2 = self._pack_fold()
             return wf, None, c1, c2
-        self._pack()
-        return self._qkv_w, self._qkv_b, None, None
+        w, b, _, _ = self._pack()
+        return w, b, None, None
 
     def _weights_out(self, f16: bool = False):
         if f16:
             if self._q4_out is not None:
                 raise NotImplementedError("precision='half' needs unquantised weights")
             w, b = self._weights_out()
-            key = _version_key(w)
-            if key != self._out16_key:
-                with torch.no_grad():
-                    self._out16 = w.data.to(torch.float16).contiguous()      # exact for |w| >= 2^-14 (bf16 has 8 significant bits)
-                    _check_fp16_range(self._out16)
-                self._out16_key = key
-            return self._out16, b
+            return self._derived.get('out16', _version_key(w), _to_f16, w), b
         if self._q4_out is not None:
             return self._q4_out.plain()
         if self.padded:
-            self._pack()
-            return self._out_w, self._out_b
+            return self._pack()[2:]
         return self.out.weight, self.out.bias
 
     # -- stages (names follow the reference) --------------------------------
@@ -460,11 +443,15 @@ class FlashMultiheadAttention(nn.Module):
         `stats_out` makes the out-projection emit the statistics of its output.  `resid32` (high-precision mode): the fp32
         residual stream, updated in place by the out-projection's epilogue; `out` receives its bf16 rounding.
         `lora_names`: on a block with LoRA adapters (ESM2.add_lora), the adapters to apply (None / empty: all of them)."""
-        if self._has_lora:
-            return self._forward_lora(x, cu_lens, max_len, lora_names, ctx, resid, alpha, out, x_stats, stats_out,
-                                      resid32 is not None or resid_pair is not None)
         T = x.shape[0]
         E = self.attn_dim                                   # width of each of q, k, v (H * padded head dim)
+        lw = None                                           # adapters: one esme_hip_lora_down in front of each GEMM that has some; that GEMM then runs over K = E + X
+        if self._has_lora:
+            if self.training:
+                raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
+            if resid32 is not None or resid_pair is not None or (ctx is not None and (ctx.f16 or ctx.exact_attn)):
+                raise NotImplementedError("LoRA adapters run in precision 'fast' only ('high', 'half' and 'exact' have no adapter path)")
+            lw = self._lora_weights(lora_names, x_stats is not None)
         H, d = self.num_heads, self.head_pad
         rot_fusable = (self.rot_emb is not None and ctx is not None and not self.pre_layernorm
                        and d in (16, 32, 64) and E % 32 == 0)
@@ -495,15 +482,14 @@ class FlashMultiheadAttention(nn.Module):
             return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out, resid_pair=resid_pair,
                                    pair_scale=pair_scale, pair_ext=pair_ext, col_absmax=g_col)
         if x_stats is not None:
-            wf, _, c1, c2 = self._weights_qkv(True, f16, pair_ext)
-            qkv = _hip.gemm_fused(x, wf, None, ln=(x_stats, self.embed_dim, self.norm.eps, c1, c2, ctx.ovf if ctx is not None else None), rot=rot,
+            a_op, wf, c1, c2 = self._qkv_operands(x, x_stats, ctx, lw, f16, pair_ext)
+            qkv = _hip.gemm_fused(a_op, wf, None, ln=(x_stats, self.embed_dim, self.norm.eps, c1, c2, ctx.ovf if ctx is not None else None), rot=rot,
                                   q_scale=_q_scale(self.head_dim) if (qp and rot_fusable) else 0.0,
                                   qk_sumsq=guard.qk[self.layer_index] if (guard is not None and rot is not None) else None)
         else:
             if self.padded:
                 raise NotImplementedError('padded layouts run the LayerNorm-folded path only')
-            w, b, _, _ = self._weights_qkv(False)
-            qkv = _hip.gemm_fused(self.norm(x), w, b, rot=rot)
+            qkv = self._qkv_lora_unfused(x, lw, rot)
         if qk_pass:
             # ESM-C: q/k LayerNorm over the full width + rotary in ONE in-place pass over q and k (+ the softmax scale on q)
             _hip.qk_norm_rotary_(qkv[:, :E], qkv[:, E:2 * E], self.layernorm_q.weight, self.layernorm_k.weight,
@@ -520,9 +506,8 @@ class FlashMultiheadAttention(nn.Module):
                     q, k = self.rot_emb(q, k, cu_lens, max_len, inplace=True)
         if ctx is not None and ctx.probe is not None:
             ctx.probe.append(_score_bound(q.reshape(T, E), k.reshape(T, E), H, d, self.head_dim ** -0.5))
-        a = self._attn(q, k, v, cu_lens, max_len, exact=bool(ctx is not None and ctx.exact_attn),
-                       order=ctx.order if ctx is not None else None, q_prescaled=qp)
-        wo, bo = self._weights_out(f16)
+        a, wo, bo = self._out_operands(lw, f16, q, k, v, cu_lens, max_len, exact=bool(ctx is not None and ctx.exact_attn),
+                                       order=ctx.order if ctx is not None else None, q_prescaled=qp)
         if resid is not None or resid32 is not None or resid_pair is not None:
             return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out, resid32=resid32, resid_pair=resid_pair,
                                    pair_scale=pair_scale, pair_ext=pair_ext, col_absmax=g_col if resid_pair is not None else None)
@@ -543,25 +528,19 @@ class FlashMultiheadAttention(nn.Module):
         mods = {p: getattr(self, p) for p in ('q', 'k', 'v', 'out') if isinstance(getattr(self, p), LoRA)}
         sel = {p: m.select(lora_names) for p, m in mods.items()}
         params = [t for p, m in mods.items() for t in m.params(sel[p])]
-        if fold:
-            self._pack_fold()
-        else:
-            self._pack()
-        key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), self._fold_key if fold else self._pack_key,
+        base = (self._pack_fold() if fold else self._pack())[0]
+        key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), self._derived.key('fold' if fold else 'pack'),
                _version_key(self.out.weight, *params))
-        if self._lora_cache is not None and self._lora_cache[0] == key:
-            return self._lora_cache[1]
         E = self.embed_dim
-        res = {'qkv': None, 'out': None}
-        with torch.no_grad():
+
+        def build():
+            res = {'qkv': None, 'out': None}
             blocks = [(i, *mods[p].stacked(sel[p])) for i, p in enumerate(('q', 'k', 'v')) if p in mods]
             if blocks:
                 A = torch.cat([b[1] for b in blocks], dim=0).contiguous()
                 X = ext_width(A.shape[0])
                 c1A = bA = None
-                base = self._qkv_w
                 if fold:
-                    base = self._fold[0]
                     Af = A.float()
                     A = (Af * self.norm.weight.data.float().unsqueeze(0)).to(torch.bfloat16).contiguous()
                     c1A = A.float().sum(dim=1).contiguous()
@@ -581,8 +560,8 @@ class FlashMultiheadAttention(nn.Module):
                 we[:, :E] = wo
                 we[:, E:E + B.shape[1]] = B.to(torch.bfloat16)
                 res['out'] = (X, A.contiguous(), we)
-        self._lora_cache = (key, res)
-        return res
+            return res
+        return self._derived.get('lora', key, build)
 
     def lora_ext_widths(self, lora_names):
         """(X of the QKV GEMM, X of the out-projection) for this selection (0: that GEMM has no adapter)."""
@@ -590,9 +569,10 @@ class FlashMultiheadAttention(nn.Module):
         return (lw['qkv'][0] if lw['qkv'] else 0, lw['out'][0] if lw['out'] else 0)
 
     def _qkv_lora_unfused(self, x, lw, rot):
-        """LayerNorm kernel -> [h | h A^T] -> plain QKV GEMM over [W | s B] (the stage form, and the path without LayerNorm fold)."""
+        """LayerNorm kernel -> [h | h A^T] -> plain QKV GEMM over [W | s B] (the stage form, and the path without LayerNorm fold);
+        without adapters (`lw` None or no q / k / v adapter selected) LayerNorm kernel -> plain QKV GEMM."""
         w, b, _, _ = self._weights_qkv(False)
-        if lw['qkv'] is None:
+        if lw is None or lw['qkv'] is None:
             return _hip.gemm_fused(self.norm(x), w, b, rot=rot)
         X, A, _, _, we = lw['qkv']
         E = self.embed_dim
@@ -601,63 +581,34 @@ class FlashMultiheadAttention(nn.Module):
         _hip.lora_down(he[:, :E], A, he[:, E:])
         return _hip.gemm_fused(he, we, b, rot=rot)
 
-    def _forward_lora(self, x, cu_lens, max_len, lora_names, ctx, resid, alpha, out, x_stats, stats_out, high):
-        """The attention branch of precision 'fast' with adapters: the launches of `forward` plus one esme_hip_lora_down in front of each GEMM
-        that has adapters; that GEMM then runs over K = E + X.  With every lora_B zero the extension adds exact zeros to the fp32
-        accumulators, so the result equals the block's without adapters bit for bit."""
-        if self.training:
-            raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
-        if high or (ctx is not None and (ctx.f16 or ctx.exact_attn)):
-            raise NotImplementedError("LoRA adapters run in precision 'fast' only ('high', 'half' and 'exact' have no adapter path)")
-        T = x.shape[0]
-        E = self.attn_dim
-        H, d = self.num_heads, self.head_pad
-        fold = x_stats is not None
-        lw = self._lora_weights(lora_names, fold)
-        rot_fusable = (self.rot_emb is not None and ctx is not None and not self.pre_layernorm and d in (16, 32, 64) and E % 32 == 0)
-        rot = (ctx.cos, ctx.sin, ctx.pos, d, 2 * E) if rot_fusable else None
-        qk_pass = (self.pre_layernorm and self.rot_emb is not None and ctx is not None and d in (16, 32, 64, 128) and E <= 5120)
-        qp = bool(_ATTN_QP and (rot_fusable or qk_pass) and d in (32, 64) and E % 64 == 0 and fold)
-        if not fold:
-            qkv = self._qkv_lora_unfused(x, lw, rot)
-        else:
-            wf, _, c1, c2 = self._weights_qkv(True)
-            a_op = x
-            if lw['qkv'] is not None:
-                X, A, c1A, bA, wf = lw['qkv']
-                xe = ctx.lora_x if ctx is not None else None
-                if xe is None or xe.data_ptr() != x.data_ptr() or xe.stride(0) != x.stride(0) or xe.shape[1] < E + X:
-                    xe = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)       # (a caller outside the model's forward: x moves once)
-                    xe[:, :E].copy_(x)
-                _hip.lora_down(xe[:, :E], A, xe[:, E:E + X], ln=(x_stats, self.embed_dim, self.norm.eps, c1A, bA))
-                a_op = xe[:, :E + X]
-            qkv = _hip.gemm_fused(a_op, wf, None, ln=(x_stats, self.embed_dim, self.norm.eps, c1, c2, None), rot=rot,
-                                  q_scale=_q_scale(self.head_dim) if (qp and rot_fusable) else 0.0)
-        if qk_pass:
-            _hip.qk_norm_rotary_(qkv[:, :E], qkv[:, E:2 * E], self.layernorm_q.weight, self.layernorm_k.weight,
-                                 self.layernorm_q.bias, self.layernorm_k.bias, self.layernorm_q.eps,
-                                 ctx.cos, ctx.sin, ctx.pos, H, q_scale=_q_scale(self.head_dim) if qp else 1.0)
-            q, k, v = (qkv[:, i * E:(i + 1) * E].view(T, H, d) for i in range(3))
-        else:
-            q, k, v = self._split_qkv(qkv)
-            if self.rot_emb is not None and rot is None:
-                if ctx is not None:
-                    _hip.rotary_(q.view(T, E), k.view(T, E), ctx.cos, ctx.sin, ctx.pos, H)
-                else:
-                    q, k = self.rot_emb(q, k, cu_lens, max_len, inplace=True)
-        order = ctx.order if ctx is not None else None
-        if lw['out'] is None:
-            a = self._attn(q, k, v, cu_lens, max_len, order=order, q_prescaled=qp)
-            wo, bo = self._weights_out()
-        else:
-            X, A, wo = lw['out']
-            bo = self.out.bias
-            a = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)
-            self._attn(q, k, v, cu_lens, max_len, order=order, q_prescaled=qp, out=a[:, :E])
-            _hip.lora_down(a[:, :E], A, a[:, E:])
-        if resid is not None:
-            return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out)
-        return _hip.gemm(a, wo, bo, out=out)
+    def _qkv_operands(self, x, x_stats, ctx, lw, f16, pair_ext):
+        """(operand, W', c1, c2) of the LayerNorm-folded QKV GEMM.  With q / k / v adapters (`lw`: _lora_weights): the operand is [x | u] with
+        u = the adapters' down-projection, written here by esme_hip_lora_down, and W' = [W' | s B | 0].  With every lora_B zero the extension
+        adds exact zeros to the fp32 accumulators, so the result equals the block's without adapters bit for bit."""
+        wf, _, c1, c2 = self._weights_qkv(True, f16, pair_ext)
+        if lw is None or lw['qkv'] is None:
+            return x, wf, c1, c2
+        X, A, c1A, bA, wf = lw['qkv']
+        E = self.embed_dim
+        xe = ctx.lora_x if ctx is not None else None
+        if xe is None or xe.data_ptr() != x.data_ptr() or xe.stride(0) != x.stride(0) or xe.shape[1] < E + X:
+            xe = torch.empty(x.shape[0], E + X, dtype=torch.bfloat16, device=x.device)       # (a caller outside the model's forward: x moves once)
+            xe[:, :E].copy_(x)
+        _hip.lora_down(xe[:, :E], A, xe[:, E:E + X], ln=(x_stats, self.embed_dim, self.norm.eps, c1A, bA))
+        return xe[:, :E + X], wf, c1, c2
+
+    def _out_operands(self, lw, f16, q, k, v, *attn_args, **attn_kw):
+        """Runs the attention kernel (_attn) and returns (its output, W_o, b_o), the operands of the out-projection.  With an out adapter
+        (`lw`: _lora_weights) the output lands in the first E columns of a (T, E + X) buffer, esme_hip_lora_down fills the rest, and
+        W_o = [W_o | s B | 0]."""
+        if lw is None or lw['out'] is None:
+            return (self._attn(q, k, v, *attn_args, **attn_kw), *self._weights_out(f16))
+        X, A, wo = lw['out']
+        E = self.embed_dim
+        a = torch.empty(q.shape[0], E + X, dtype=torch.bfloat16, device=wo.device)
+        self._attn(q, k, v, *attn_args, out=a[:, :E], **attn_kw)
+        _hip.lora_down(a[:, :E], A, a[:, E:])
+        return a, wo, self.out.bias
 
 
 class SwiGLU(nn.Module):
@@ -672,24 +623,21 @@ class SwiGLU(nn.Module):
         self.in_features, self.out_features = in_features, out_features
         self.activation = Linear(in_features, out_features, bias=False, dtype=dtype)
         self.fc = Linear(in_features, out_features, bias=False, dtype=dtype)
-        self._packed: Optional[torch.Tensor] = None
-        self._pack_key = None
+        self._derived = Derived()   # 'pack': the interleaved weight
 
     def _pack(self):
-        key = _version_key(self.activation.weight, self.fc.weight)
-        if key == self._pack_key:
-            return
+        return self._derived.get('pack', _version_key(self.activation.weight, self.fc.weight), self._build_pack)
+
+    def _build_pack(self):
         F, E = self.activation.weight.shape
         assert F % 32 == 0
-        with torch.no_grad():
-            g = self.activation.weight.data.view(F // 32, 1, 32, E)
-            f = self.fc.weight.data.view(F // 32, 1, 32, E)
-            self._packed = torch.cat((g, f), dim=1).reshape(2 * F, E).contiguous()
-        self._pack_key = key
+        g = self.activation.weight.data.view(F // 32, 1, 32, E)
+        f = self.fc.weight.data.view(F // 32, 1, 32, E)
+        return torch.cat((g, f), dim=1).reshape(2 * F, E).contiguous()
 
     def forward(self, x, out=None, ln=None, packed=None):
-        self._pack()
-        return _hip.gemm_fused(x, self._packed if packed is None else packed, None, _hip.EPI_SWIGLU, out=out, ln=ln)
+        w = self._pack()
+        return _hip.gemm_fused(x, w if packed is None else packed, None, _hip.EPI_SWIGLU, out=out, ln=ln)
 
 
 class FlashTransformerLayer(nn.Module):
@@ -704,9 +652,9 @@ class FlashTransformerLayer(nn.Module):
                                                  phys_dim=phys_dim, head_pad=head_pad)
         self.phys_dim = self.self_attn.phys_dim
         self.padded = self.self_attn.padded
-        self._down_pad = None
-        self._down_key = None
-        self._up_pad = None         # (key, up-projection weight with zero pad columns): precision 'exact' on padded layouts
+        # derived weight copies: 'fold' / 'fold16' / 'fold16x' of the FFN up-projection (as in FlashMultiheadAttention), 'down16' the float16
+        # down-projection weight, 'down_pad' / 'up_pad' the down / up projection with zero pad rows / columns (padded layouts)
+        self._derived = Derived()
         if final_activation == 'swiglu':
             width = int(((expand_dim * embed_dim) + 255) // 256 * 256)
             self.final = nn.Sequential(LayerNorm(embed_dim, dtype=dtype),
@@ -720,73 +668,44 @@ class FlashTransformerLayer(nn.Module):
         else:
             raise ValueError('Invalid final activation function. Must be "swiglu" or "gelu".')
         self.final_activation = final_activation
-        self._fold = None
-        self._fold_key = None
-        self._fold16 = None         # float16 forms (precision 'half'): folded up-projection (W * pow2(gamma)), down-projection weight
-        self._fold16_key = None
-        self._rho16 = None          # (rho, 1 / rho) of the FFN LayerNorm (see FlashMultiheadAttention._rho16)
-        self._fold16x = None        # (key, the up-projection weight with the extension K-tile)
-        self._down16 = None
-        self._down16_key = None
         self._q4_up = None          # esme.quantization.Q4Matrix pair when the layer is 4-bit
         self._q4_down = None
 
-    def _pack_fold(self, f16: bool = False):
-        """LN-folded copy of the FFN up-projection weight (self.final[0] folded in); `f16`: in float16 (precision 'half')."""
+    def _fold_operands(self):
         ln = self.final[0]
         beta = ln.bias.data if ln.bias is not None else None
-        dt = torch.float16 if f16 else torch.bfloat16
-        have = self._fold16_key if f16 else self._fold_key
-        fold = None
+        if self.final_activation == 'gelu':
+            up, Ep = self.final[1], self.phys_dim
+            return _pad_last(up.weight.data, Ep), up.bias.data if up.bias is not None else None, _pad_last(ln.weight.data, Ep), _pad_last(beta, Ep)
+        return self.final[1]._pack(), None, ln.weight.data, beta
+
+    def _pack_fold(self, f16: bool = False):
+        """LN-folded copy of the FFN up-projection weight (self.final[0] folded in): (W', c1, c2); `f16`: ((W', c1, c2), (rho, 1 / rho)) with
+        W' in float16 (precision 'half')."""
+        ln = self.final[0]
         if self.final_activation == 'gelu':
             up = self.final[1]
             key = _version_key(up.weight, up.bias, ln.weight, ln.bias)
-            if key != have:
-                with torch.no_grad():
-                    Ep = self.phys_dim
-                    args = (_pad_last(up.weight.data, Ep), up.bias.data if up.bias is not None else None, _pad_last(ln.weight.data, Ep), _pad_last(beta, Ep))
-                    if f16:
-                        *fold, rho, rho_inv = _fold_layernorm_pow2(*args)
-                        fold, self._rho16 = tuple(fold), (rho, rho_inv)
-                    else:
-                        fold = _fold_layernorm(*args, dt)
         else:
             sw = self.final[1]
             sw._pack()
-            key = (sw._pack_key, _version_key(ln.weight, ln.bias))
-            if key != have:
-                with torch.no_grad():
-                    if f16:
-                        *fold, rho, rho_inv = _fold_layernorm_pow2(sw._packed, None, ln.weight.data, beta)
-                        fold, self._rho16 = tuple(fold), (rho, rho_inv)
-                    else:
-                        fold = _fold_layernorm(sw._packed, None, ln.weight.data, beta, dt)
-        if fold is not None:
-            if f16:
-                self._fold16, self._fold16_key = fold, key
-            else:
-                self._fold, self._fold_key = fold, key
-        return self._fold16 if f16 else self._fold
+            key = (sw._derived.key('pack'), _version_key(ln.weight, ln.bias))
+        return self._derived.get('fold16' if f16 else 'fold', key, _build_fold, f16, self._fold_operands)
 
     def stream_scale(self):
         """precision 'half': (rho, 1 / rho) of the FFN LayerNorm (the scaling the pair stream carries into the up-projection)."""
         if self._q4_up is not None:
             raise NotImplementedError("precision='half' runs the LayerNorm-folded path on unquantised weights")
-        self._pack_fold(True)
-        return self._rho16
+        return self._pack_fold(True)[1]
 
     def _weights_up(self, fold: bool, f16: bool = False, ext_sel: Optional[torch.Tensor] = None):
         """(W, bias, c1, c2) of the FFN up-projection (gate/fc interleaved for SwiGLU); `ext_sel`: with the extension K-tile (_extend_k)."""
         if f16:
             if self._q4_up is not None or not fold:
                 raise NotImplementedError("precision='half' runs the LayerNorm-folded path on unquantised weights")
-            wf, c1, c2 = self._pack_fold(True)
+            (wf, c1, c2), _ = self._pack_fold(True)
             if ext_sel is not None:
-                key = (self._fold16_key, _ext_key(ext_sel))
-                if self._fold16x is None or self._fold16x[0] != key:
-                    with torch.no_grad():
-                        self._fold16x = (key, _extend_k(wf, ext_sel))
-                wf = self._fold16x[1]
+                wf = self._derived.get('fold16x', (self._derived.key('fold16'), _ext_key(ext_sel)), _extend_k, wf, ext_sel)      # (keyed on the channel LIST, not the tensor's address: ADVICE r5)
             return wf, None, c1, c2
         if self._q4_up is not None:
             if fold:
@@ -800,39 +719,23 @@ class FlashTransformerLayer(nn.Module):
             if self.final_activation != 'gelu':
                 raise NotImplementedError('padded layouts are implemented for the ESM-2 block')
             up = self.final[1]
-            key = _version_key(up.weight)
-            if self._up_pad is None or self._up_pad[0] != key:
-                with torch.no_grad():
-                    self._up_pad = (key, _pad_last(up.weight.data, self.phys_dim))
-            return self._up_pad[1], up.bias, None, None
+            return self._derived.get('up_pad', _version_key(up.weight), lambda: _pad_last(up.weight.data, self.phys_dim)), up.bias, None, None
         if self.final_activation == 'gelu':
             return self.final[1].weight, self.final[1].bias, None, None
-        self.final[1]._pack()
-        return self.final[1]._packed, None, None, None
+        return self.final[1]._pack(), None, None, None
 
     def _weights_down(self, f16: bool = False):
         if f16:
             if self._q4_down is not None:
                 raise NotImplementedError("precision='half' needs unquantised weights")
             w, b = self._weights_down()
-            key = _version_key(w)
-            if key != self._down16_key:
-                with torch.no_grad():
-                    self._down16 = w.data.to(torch.float16).contiguous()
-                    _check_fp16_range(self._down16)
-                self._down16_key = key
-            return self._down16, b
+            return self._derived.get('down16', _version_key(w), _to_f16, w), b
         if self._q4_down is not None:
             return self._q4_down.plain()
         down = self.final[3] if self.final_activation == 'gelu' else self.final[2]
         if self.padded:                                     # zero rows / bias entries for the pad columns of the stream
-            key = _version_key(down.weight, down.bias)
-            if key != self._down_key:
-                with torch.no_grad():
-                    self._down_pad = (_pad_rows(down.weight.data, self.phys_dim),
-                                      _pad_last(down.bias.data, self.phys_dim) if down.bias is not None else None)
-                self._down_key = key
-            return self._down_pad
+            return self._derived.get('down_pad', _version_key(down.weight, down.bias), lambda: (
+                _pad_rows(down.weight.data, self.phys_dim), _pad_last(down.bias.data, self.phys_dim) if down.bias is not None else None))
         return down.weight, down.bias
 
     def _ffn(self, x, resid, alpha, out, x_stats=None, stats_out=None, resid32=None, resid_pair=None, pair_scale=None, pair_ext=None, ovf=None, col_absmax=None):

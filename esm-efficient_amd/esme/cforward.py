@@ -145,7 +145,7 @@ class ModelDescriptor:
     def supported(model, precision: str = 'fast') -> bool:
         if not len(model.layers) or model.precision != precision or model.phys_dim % 64:
             return False
-        if getattr(model, 'has_lora', False):       # LoRA adapters run on the module path (esme.attention._forward_lora); the descriptor has no slot for them
+        if getattr(model, 'has_lora', False):       # LoRA adapters run on the module path (FlashMultiheadAttention.forward); the descriptor has no slot for them
             return False
         if precision == 'exact':                    # nothing is folded in this mode; the split-operand kernels cover head dims 16 / 32 / 64 / 128
             att = model.layers[0].self_attn

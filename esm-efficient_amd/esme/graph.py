@@ -18,21 +18,12 @@ from collections import OrderedDict
 
 import torch
 
-# attributes under which modules cache DERIVED device tensors (packed / LayerNorm-folded / padded weight copies,
-# rotary tables): allocated outside a graph's private pool, read by the captured kernels through raw pointers
-_DERIVED_ATTRS = ('_qkv_w', '_qkv_b', '_fold', '_out_w', '_out_b', '_down_pad', '_packed', '_pad', '_embed_pad',
-                  '_cos_cached', '_sin_cached', '_fold16', '_out16', '_down16', '_rho16', '_fold16x', '_half_ovf', '_up_pad', '_table_cache')
+from esme.nn import Derived, flatten_tensors
 
-
-def _flatten(x):
-    if isinstance(x, torch.Tensor):
-        yield x
-    elif isinstance(x, (tuple, list)):
-        for y in x:
-            yield from _flatten(y)
-    elif isinstance(x, dict):
-        for y in x.values():
-            yield from _flatten(y)
+# DERIVED device tensors (packed / LayerNorm-folded / padded weight copies, rotary tables) are allocated outside a graph's private pool and
+# read by the captured kernels through raw pointers.  The transformer block keeps its own in an esme.nn.Derived per module (found by type,
+# whatever it holds); these are the attributes under which the other modules cache theirs
+_DERIVED_ATTRS = ('_pad', '_embed_pad', '_cos_cached', '_sin_cached', '_half_ovf', '_table_cache')
 
 
 def external_tensors(model):
@@ -42,8 +33,11 @@ def external_tensors(model):
     be freed while an older graph still holds their addresses."""
     keep = []
     for m in model.modules():
+        for v in vars(m).values():
+            if isinstance(v, Derived):
+                keep.extend(v.tensors())
         for a in _DERIVED_ATTRS:
-            keep.extend(_flatten(getattr(m, a, None)))
+            keep.extend(flatten_tensors(getattr(m, a, None)))
     keep.extend(p.data for p in model.parameters())
     plan = getattr(model, '_half_plan', None)             # precision 'half': the massive-channel list the extension K-tile kernels read
     if plan is not None and getattr(plan, 'ext_sel', None) is not None:

@@ -42,6 +42,51 @@ def weights_epoch() -> int:
     return _WEIGHTS_EPOCH[0]
 
 
+def flatten_tensors(x):
+    """Every tensor inside nested tuples / lists / dicts."""
+    if isinstance(x, torch.Tensor):
+        yield x
+    elif isinstance(x, (tuple, list)):
+        for y in x:
+            yield from flatten_tensors(y)
+    elif isinstance(x, dict):
+        for y in x.values():
+            yield from flatten_tensors(y)
+
+
+class Derived:
+    """The derived weight copies of ONE module (packed, LayerNorm-folded, fp16, extension-tile, padded, adapter forms): name -> (key, value).
+    Everything a module's kernels read that is not a parameter lives here, so esme.graph.external_tensors finds it without knowing names."""
+    __slots__ = ('_entries',)
+
+    def __init__(self):
+        self._entries = {}
+
+    def get(self, name, key, build, *args, rekey=None):
+        """The value cached under `name` if it was built for `key`, else build(*args) (under no_grad), stored.  `rekey`: forms the key to
+        store AFTER the build, for a builder that moves the tensors the key is made of.  (On the forward path: a hit costs one dict lookup
+        and the comparison, so callers pass a function and its arguments rather than a closure made per call.)"""
+        e = self._entries.get(name)
+        if e is not None and e[0] == key:
+            return e[1]
+        with torch.no_grad():
+            value = build(*args)
+        self._entries[name] = (key if rekey is None else rekey(), value)
+        return value
+
+    def key(self, name):
+        e = self._entries.get(name)
+        return None if e is None else e[0]
+
+    def clear(self, *names):
+        for n in names or tuple(self._entries):
+            self._entries.pop(n, None)
+
+    def tensors(self):
+        for _, value in self._entries.values():
+            yield from flatten_tensors(value)
+
+
 class _TrackedModule(nn.Module):
     def __setattr__(self, name, value):
         if name in ('weight', 'bias'):

@@ -202,7 +202,7 @@ def quantize_layer_(layer, quant_type: str, scratch: WeightScratch):
         _repoint(q4[:3], codes, absmax)
         bias = torch.cat([m.bias.data for m in q4[:3]]).contiguous() if q4[0].bias is not None else None
         att.q, att.k, att.v, att.out = q4
-        att._qkv_w = att._qkv_b = att._fold = att._pack_key = att._fold_key = None
+        att._derived.clear()                  # (copies of the bfloat16 weights that are gone)
         att._q4_qkv = Q4Matrix(codes, absmax, bias, quant_type, scratch, ln=att.norm)
         att._q4_out = Q4Matrix(q4[3].weight.data, q4[3].absmax, q4[3].bias.data if q4[3].bias is not None else None,
                                quant_type, scratch)
@@ -225,12 +225,12 @@ def quantize_layer_(layer, quant_type: str, scratch: WeightScratch):
             pa = torch.cat((gate.absmax.view(F // 32, 1, 32, -1), fc.absmax.view(F // 32, 1, 32, -1)),
                            dim=1).reshape(2 * F, -1).contiguous()
             sw.activation, sw.fc = gate, fc
-            sw._packed = sw._pack_key = None
+            sw._derived.clear()
             layer.final[2] = down
             layer._q4_up = Q4Matrix(pc, pa, None, quant_type, scratch, ln=ln)
         layer._q4_down = Q4Matrix(down.weight.data, down.absmax, down.bias.data if down.bias is not None else None,
                                   quant_type, scratch)
-        layer._fold = layer._fold_key = None
+        layer._derived.clear()
     return layer
 
 

@@ -308,14 +308,14 @@ def test_qkv_packing_keeps_state_dict():
     m = ESM2(num_layers=1, embed_dim=64, attention_heads=4)
     att = m.layers[0].self_attn
     before = {k: v.clone() for k, v in m.state_dict().items()}
-    att._pack()
+    qkv_w = att._pack()[0]
     after = m.state_dict()
     assert set(before) == set(after) and all(torch.equal(before[k], after[k]) for k in before)
-    assert att._qkv_w.shape == (192, 64) and att.q.weight.data_ptr() == att._qkv_w.data_ptr()
-    assert att.k.weight.data_ptr() == att._qkv_w[64:].data_ptr()
-    key = att._pack_key
-    att._pack()
-    assert att._pack_key == key                            # idempotent
+    assert qkv_w.shape == (192, 64) and att.q.weight.data_ptr() == qkv_w.data_ptr()
+    assert att.k.weight.data_ptr() == qkv_w[64:].data_ptr()
+    key = att._derived.key('pack')
+    assert key is not None
+    assert att._pack()[0] is qkv_w and att._derived.key('pack') == key      # idempotent
 
 
 def test_synthetic_batches_and_flops():
