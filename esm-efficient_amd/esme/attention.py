@@ -136,7 +136,7 @@ def _fold_layernorm(w: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.
 
 
 class HalfPlan:
-    """What precision 'half' runs for ONE model, decided by a calibration forward (esme.esm.ESM2._calibrate_half):
+    """What precision 'half' runs for ONE model, decided by a calibration forward (esme.halfmode.calibrate):
 
       ext_sel   int32 device tensor of <= 64 ascending stream channels whose largest |value| at some stream site is `ratio` times the median
                 channel's ("massive" channels), or None.  Their lo half rides to the LayerNorm-folded GEMMs in an extension K-tile
@@ -176,6 +176,16 @@ class HalfPlan:
         return f"ext channels {0 if self.ext_sel is None else self.ext_sel.numel()}, q/k pairs {'on' if self.qk_pair else 'off'}{where}" + (', fixed-reference attention' if self.qp else '')
 
 
+def has_pair_form(att) -> bool:
+    """The block of attention module `att` has a q/k-pair form (HalfPlan.qk_pair): no q/k LayerNorm, head dim <= 64, width a multiple of 128."""
+    return (not att.pre_layernorm) and att.head_pad in (16, 32, 64) and att.attn_dim % 128 == 0
+
+
+def has_fixed_reference_form(att) -> bool:
+    """The block may run the fp16 attention kernel in its fixed-reference form (HalfPlan.qp): fused rotary, head dim 32 / 64, unpadded."""
+    return att.rot_emb is not None and att.head_pad in (32, 64) and att.attn_dim % 64 == 0 and not att.padded
+
+
 def _ext_key(ext_sel: torch.Tensor):
     """Host tuple of an extension-tile channel list (set by HalfPlan; computed once for a bare tensor)."""
     key = getattr(ext_sel, '_esme_key', None)
@@ -190,7 +200,7 @@ class HalfGuard:
 
       col   (2 L + 1, phys_dim): row 0 = max |value| per stream column at the start (the embedding output, where a token-triggered massive channel
             is most visible), row 1 + 2 i after layer i's attention branch, row 2 + 2 i after its FFN branch -- of the STORED stream, i.e. times
-            the column scaling of the LayerNorm that reads it next (ESM2._guard_scales undoes it);
+            the column scaling of the LayerNorm that reads it next (esme.halfmode.guard_scales undoes it);
       qk    (L, 2, heads): max over rows of the squared row norm of q (then k) per head, for layers whose q / k are single fp16 values and whose
             rotary is fused into the projection (ESM-2 / ESM-1 blocks) or pass through ESM-C's q / k pass (zeros elsewhere: not covered).
       q_scaled  the unit of qk[:, 0]: True when its q norms carry softmax_scale * log2(e) squared -- the LN-folded projection records q AFTER

@@ -24,7 +24,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
-from esme import _hip
+from esme import _hip, halfmode
 from esme.alphabet import Alphabet, Alphabet3
 from esme.attention import FlashTransformerLayer, ForwardContext
 from esme.head import RobertaLMHead
@@ -101,6 +101,7 @@ class ESM2(nn.Module):
         self._embed_pad_key = None
         self.checkpointing = False
         self.embed_scale = 1
+        self.half_mode = halfmode.HalfState()      # precision 'half': plan, guard, range flag (esme.halfmode)
         self.embed_tokens = nn.Embedding(self.vocab_size, embed_dim, dtype=dtype,
                                          padding_idx=self.alphabet.padding_idx)
         self.embed_tokens.weight.requires_grad_(False)
@@ -202,268 +203,20 @@ class ESM2(nn.Module):
         assert mode in ('fast', 'high', 'half', 'exact'), mode
         if mode != 'fast' and self.has_lora:
             raise NotImplementedError(f"precision {mode!r} has no LoRA adapter path: adapters run in precision 'fast' only")
-        from esme.attention import HalfPlan
         changed = mode != self.precision
         self.precision = mode
-        if isinstance(robust, HalfPlan):
-            self._half_plan, changed = robust, True
-        elif robust is not None:
-            assert robust in ('auto', True, False), robust
-            if robust != self.half_robust:                    # (only a CHANGE drops the plan: set_precision('half') on a calibrated model keeps it)
-                self._half_plan, changed = None, True
-            self.half_robust = robust
-        if calib is not None:
-            tokens, rest = calib
-            cu = rest[0] if isinstance(rest, (tuple, list)) else rest
-            self._half_calib = (tokens.detach().reshape(-1).cpu().to(torch.int64), cu.detach().reshape(-1).cpu().to(torch.int32))
-            self._half_plan, changed = None, True
-        if changed:
+        if halfmode.configure(self, robust, calib) or changed:
             self._drop_derived()                              # (keeps the plan just decided on; invalidate_graphs() would recalibrate)
         return self
 
     def half_plan(self, device=None):
         """The HalfPlan precision 'half' runs with on this model (calibrated on first use; see `half_robust`)."""
-        from esme.attention import HalfPlan
-        plan = getattr(self, '_half_plan', None)
-        if plan is None:
-            if self.half_robust is False or not len(self.layers):
-                plan = HalfPlan(info={'calibrated': False})
-            else:
-                plan = self._calibrate_half(device if device is not None else self.embed_tokens.weight.device)
-            self._half_plan = plan
-        return plan
+        return halfmode.half_plan(self, device)
 
-    def _calibration_batch(self):
-        """The built-in calibration input: 8 sequences / 1 024 tokens from numpy PCG64 (the same on every machine) -- residues 4..23 with, for
-        HALF_CALIB_VOCAB = 'all', EVERY other id of the alphabet (<unk>, X B U Z O . -, <null_1> / |, <mask>; not <pad>, which never occurs in a
-        packed input) sprinkled over 8 interior positions each, <cls> / <eos> at the ends; then the caller's own batch if one was given
-        (set_precision(..., calib=)).  Returns (tokens int64, cu_lens int32, max_len) on the host."""
-        import numpy as np
-        rng = np.random.Generator(np.random.PCG64(20250929))
-        al = self.alphabet
-        lengths = [192, 160, 160, 128, 128, 96, 96, 64]
-        toks = [np.concatenate(([al.cls_idx], rng.integers(4, 24, size=n - 2), [al.eos_idx])) for n in lengths]
-        tokens = np.concatenate(toks).astype(np.int64)
-        if self.HALF_CALIB_VOCAB == 'all':
-            starts = np.concatenate(([0], np.cumsum(lengths)))
-            interior = np.ones(tokens.size, dtype=bool)
-            interior[starts[:-1]] = False
-            interior[starts[1:] - 1] = False
-            others = [i for i in range(len(al.alphabet)) if not (4 <= i < 24) and i not in (al.cls_idx, al.eos_idx, al.padding_idx)]
-            spots = rng.choice(np.nonzero(interior)[0], size=8 * len(others), replace=False)
-            tokens[spots] = np.repeat(np.asarray(others, dtype=np.int64), 8)
-        lengths = list(lengths)
-        user = getattr(self, '_half_calib', None)
-        if user is not None:
-            ut, ucu = user
-            tokens = np.concatenate((tokens, ut.numpy()))
-            lengths += [int(b - a) for a, b in zip(ucu[:-1].tolist(), ucu[1:].tolist())]
-        cu = np.concatenate(([0], np.cumsum(lengths))).astype(np.int32)
-        return torch.from_numpy(tokens), torch.from_numpy(cu), int(max(lengths))
-
-    def _guard_scales(self, device):
-        """(2 L + 1, phys_dim) float32: the per-column scaling the STORED pair stream carries at each guard site (HalfGuard.col rows): rho of layer 0's
-        attention LayerNorm at the start, rho of the FFN LayerNorm after layer i's attention branch, rho of layer i + 1's attention LayerNorm after
-        its FFN branch, 1 after the last layer."""
-        L = len(self.layers)                    # (stream_scale() is cached per layer on the parameters' versions; this runs at synchronisation points only)
-        rows = [self.layers[0].self_attn.stream_scale()[0]]
-        for i, layer in enumerate(self.layers):
-            rows.append(layer.stream_scale()[0])
-            rows.append(self.layers[i + 1].self_attn.stream_scale()[0] if i + 1 < L else torch.ones(self.phys_dim, dtype=torch.float32, device=device))
-        return torch.stack([r.to(device) for r in rows])
-
-    def _guard_measure(self, guard, device, site_ref=None):
-        """(channel ratio (E,), score bound per layer (L,), covered (L,) bool) from a HalfGuard's device maxima -- device tensors, no sync.
-        ratio[c] = max over the sites of  max_t |x[t, c]| / median_c' max_t |x[t, c']|  (0 where a site saw nothing).  `site_ref`: the calibration's
-        medians, a floor for the reference (a batch of a few rows has widely scattered per-channel maxima: 1 row of N(0, 1) values reaches 6.4 x its median)."""
-        E = self.embed_dim
-        x = guard.col.view(torch.float32)[:, :E] / self._guard_scales(device)[:, :E]
-        med = x.median(dim=1).values
-        self._last_site_median = med
-        if site_ref is not None:
-            med = torch.where(med > 0, torch.maximum(med, site_ref.to(device)), med)
-        ratio = torch.where(med[:, None] > 0, x / med[:, None].clamp_min(1e-30), torch.zeros_like(x)).amax(dim=0)
-        qk = guard.qk.view(torch.float32)
-        att = self.layers[0].self_attn
-        # the unit the q norms were RECORDED in (HalfGuard.q_scaled), not the current plan's: a plan change between the forwards and this reading
-        # would otherwise mis-scale the bound by softmax_scale * log2(e)
-        bound = (qk[:, 0] * qk[:, 1]).sqrt().amax(dim=1) * ((1.0 / 1.4426950408889634) if guard.q_scaled else att.head_dim ** -0.5)
-        return ratio, bound, qk.amax(dim=(1, 2)) > 0
-
-    def _calibrate_half(self, device):
-        """One forward of the plain 'half' form over the calibration batch (_calibration_batch: the whole vocabulary, + the caller's own data if
-        given), measured by the SAME device maxima the run-time guard keeps (HalfGuard: largest |value| of every stream channel after every
-        branch of every layer and at the start relative to the median channel's; squared q / k row norms per head) plus, for blocks
-        whose projection does not carry the q / k guard (ESM-C, head dim 128, no rotary), a torch-side bound of |score| per layer."""
-        from esme.attention import HalfPlan, HalfGuard
-        tokens, cu, max_len = self._calibration_batch()
-        tokens, cu = tokens.to(device), cu.to(device)
-        att = self.layers[0].self_attn
-        L = len(self.layers)
-        guard = HalfGuard(L, self.phys_dim, att.num_heads, device)
-        saved = (self.precision, getattr(self, '_half_guard', None))
-        self._half_plan = HalfPlan(info={'calibrating': True})          # the plain form, and no recursion
-        probe = []
-        self._calib_probe, self._half_guard, self.precision = probe, guard, 'half'
-        try:
-            with torch.no_grad():
-                self._forward_representation(tokens, (cu, max_len), False, None, [L - 1])      # (`layers=`: the module-by-module path, which feeds the probe)
-        except BaseException:
-            self._half_plan = None                                      # (ADVICE r5: no half-built plan survives a failed calibration)
-            raise
-        finally:
-            self._calib_probe = None
-            self.precision, self._half_guard = saved
-        ratio, g_bound, covered = self._guard_measure(guard, device)
-        bounds = [float(b) for b in torch.stack(probe).tolist()] if probe else []        # one per layer, in layer order (torch-side, every layout)
-        if len(bounds) == L:                                                              # the kernels' own figure where they keep one: the larger counts
-            bounds = [max(b, float(g)) if c else b for b, g, c in zip(bounds, g_bound.tolist(), covered.tolist())]
-        bound = max(bounds) if bounds else 0.0
-        mass = torch.nonzero(ratio > self.HALF_CHANNEL_RATIO).flatten()
-        n_mass = int(mass.numel())
-        if n_mass > 64:
-            mass = mass[torch.argsort(ratio[mass], descending=True)[:64]]
-        sel = torch.sort(mass).values.to(torch.int32).contiguous() if mass.numel() else None
-        pair_ok = (not att.pre_layernorm) and att.head_pad in (16, 32, 64) and att.attn_dim % 128 == 0
-        qk_pair = pair_ok and (bound >= self.HALF_SCORE_BOUND or self.half_robust is True)
-        if bound >= self.HALF_SCORE_BOUND and not pair_ok:
-            import warnings
-            warnings.warn(f"precision='half': attention scores of this model can reach |s| ~ {bound:.0f}, where fp16 q / k cost more than 1e-3, and its block "
-                          "(q/k LayerNorm, head dim 128 or a width that is not a multiple of 128) has no q/k-pair form; use precision 'exact' if 1e-3 must hold")
-        # the pair form is paid per layer: only where that layer's own bound asks for it (robust=True: everywhere)
-        flags = None if (self.half_robust is True or len(bounds) != L) else [b >= self.HALF_SCORE_BOUND for b in bounds]
-        others = ratio.clone()
-        if sel is not None:
-            others[sel.long()] = 0
-        info = {'calibrated': True, 'calibration_tokens': int(tokens.numel()), 'vocabulary': self.HALF_CALIB_VOCAB + (' + user batch' if getattr(self, '_half_calib', None) is not None else ''),
-                'max_channel_ratio': float(ratio.max()), 'max_unselected_channel_ratio': float(others.max()), 'score_bound': bound,
-                'massive_channels': n_mass, 'qk_pair_supported': bool(pair_ok), 'qk_pair_layers': (L if flags is None else sum(flags)) if qk_pair else 0,
-                'score_guard_layers': int(covered.sum()), 'score_bounds': [round(b, 2) for b in bounds]}
-        # the fixed-reference form of the fp16 attention kernel (round 6): where the kernels have it and every layer that would use it stays below HALF_QP_BOUND
-        qp_ok = (att.rot_emb is not None and att.head_pad in (32, 64) and att.attn_dim % 64 == 0 and not att.padded and len(bounds) == L)
-        plain = [b for i, b in enumerate(bounds) if not (qk_pair and (flags is None or flags[i]))]
-        qp = bool(self.half_qp and qp_ok and plain and max(plain) < self.HALF_QP_BOUND)
-        info['fixed_reference_attention'] = qp
-        return HalfPlan(sel, qk_pair, info, qk_layers=flags, site_ref=self._last_site_median.clone(), qp=qp)
-
-    # -- the plan checked against the data (round 6) -----------------------------------------------------------------------
-    def _guard_buffers(self, device, plan=None):
-        """The model's HalfGuard (created with the first 'half' forward on `device`; None when half_guard is off), its q norms in the unit the
-        forwards of `plan` record them in (HalfGuard.q_scaled: the LN-folded projection of an ESM-2 block records q after the plan's q scale)."""
-        if not self.half_guard or not len(self.layers):
-            return None
-        g = getattr(self, '_half_guard', None)
-        if g is None or g.col.device != torch.device(device) or g.col.shape != (2 * len(self.layers) + 1, self.phys_dim):
-            from esme.attention import HalfGuard
-            g = self._half_guard = HalfGuard(len(self.layers), self.phys_dim, self.layers[0].self_attn.num_heads, device)
-        if plan is not None and not torch.cuda.is_current_stream_capturing():      # (a capture follows warm-up forwards of the same plan)
-            from esme.attention import _q_scale
-            att = self.layers[0].self_attn
-            g.rescale_q(plan.qp and not att.pre_layernorm, _q_scale(att.head_dim))
-        return g
-
-    def _plan_masks(self, plan, dev):
-        """(selected-channel mask (E,) bool, per-layer pair flags (L,) bool) of `plan` on the device, built once per plan."""
-        c = self.__dict__.get('_plan_masks_cache')
-        if c is None or c[0] is not plan or c[1].device != torch.device(dev):
-            sel_mask = torch.zeros(self.embed_dim, dtype=torch.bool, device=dev)
-            if plan.ext_sel is not None:
-                sel_mask[plan.ext_sel.long()] = True
-            flags = torch.tensor([plan.pairs_at(i) for i in range(len(self.layers))], dtype=torch.bool, device=dev)
-            c = self.__dict__['_plan_masks_cache'] = (plan, sel_mask, flags)
-        return c[1], c[2]
-
-    def _guard_snapshot(self):
-        """Device-side half of check_plan (no synchronisation): float32 vector [stale, ratio (E), score bound (L), covered (L)] of everything the
-        guard saw since it was last cleared, judged against the CURRENT plan; the maxima are cleared.  None when there is nothing to check.
-        esme.pipeline.StreamedInference downloads it with each result."""
-        g = getattr(self, '_half_guard', None)
-        if g is None or self.precision != 'half' or torch.cuda.is_current_stream_capturing():
-            return None
-        plan = self.half_plan()
-        if not plan.info.get('calibrated', False):
-            g.clear()
-            return None                                           # (robust=False: the caller asked for the plain form; nothing to hold it to)
-        dev = g.col.device
-        ratio, bound, covered = self._guard_measure(g, dev, plan.site_ref)
-        sel_mask, flags = self._plan_masks(plan, dev)
-        bad_c = (ratio > self.HALF_CHANNEL_RATIO) & ~sel_mask
-        bad_l = (bound >= self.HALF_SCORE_BOUND) & ~flags & covered
-        stale = (bad_c.any() | bad_l.any()).to(torch.float32).reshape(1)
-        g.clear()
-        return torch.cat((stale, ratio, bound, covered.to(torch.float32)))
-
-    def _plan_verdict(self, vec, update: bool = True, where: str = ''):
-        """Host-side half of check_plan: `vec` = a _guard_snapshot() on the host.  None when the plan held; else the verdict dict (and, with
-        `update`, the widened plan installed).  What no plan can cover (more than 64 massive channels; large scores in a block without a q/k-pair
-        form) leaves the plan, its descriptors and graphs as they are: with `update` it is recorded in plan.info['uncovered'] and warned about once
-        per plan; without, nothing is written (and the warning repeats until an updating check has recorded it)."""
-        if vec is None or float(vec[0]) == 0.0:
-            return None
-        E, L = self.embed_dim, len(self.layers)
-        ratio, bound, covered = vec[1:1 + E], vec[1 + E:1 + E + L], vec[1 + E + L:1 + E + 2 * L] > 0
-        plan = self.half_plan()
-        sel_mask = torch.zeros(E, dtype=torch.bool)
-        if plan.ext_key:
-            sel_mask[list(plan.ext_key)] = True
-        flags = torch.tensor([plan.pairs_at(i) for i in range(L)], dtype=torch.bool)
-        bad_c = (ratio > self.HALF_CHANNEL_RATIO) & ~sel_mask
-        bad_l = (bound >= self.HALF_SCORE_BOUND) & ~flags & covered
-        if not bool(bad_c.any() | bad_l.any()):
-            return None                                           # (judged against a plan that has been widened since the snapshot was taken)
-        chans = [(int(c), round(float(ratio[c]), 2)) for c in torch.nonzero(bad_c).flatten().tolist()]
-        layers = [(int(i), round(float(bound[i]), 1)) for i in torch.nonzero(bad_l).flatten().tolist()]
-        att = self.layers[0].self_attn
-        pair_ok = (not att.pre_layernorm) and att.head_pad in (16, 32, 64) and att.attn_dim % 128 == 0
-        verdict = {'channels': chans, 'layers': layers, 'updated': False}
-        msg = (f"precision='half': the plan is stale for this data{where} -- {len(chans)} stream channel(s) outside the extension tile reach "
-               f"{max([r for _, r in chans], default=0):.1f}x the median channel (threshold {self.HALF_CHANNEL_RATIO}), "
-               f"{len(layers)} layer(s) without q/k pairs reach a score bound of {max([b for _, b in layers], default=0):.0f} (threshold {self.HALF_SCORE_BOUND}); "
-               "results computed since the last check may miss the mode's 1e-3.")
-        # the widest plan that could cover this: the current selection stays, offenders join (largest first, up to 64); offending layers get pairs where the block has them
-        merged = torch.where(sel_mask, torch.full_like(ratio, float('inf')), ratio)
-        cand = torch.nonzero(sel_mask | bad_c).flatten()
-        if cand.numel() > 64:
-            cand = cand[torch.argsort(merged[cand], descending=True)[:64]]
-        cand = torch.sort(cand).values
-        new_flags = [bool(f) or (pair_ok and bool(b)) for f, b in zip(flags.tolist(), bad_l.tolist())]
-        new_mask = torch.zeros(E, dtype=torch.bool)
-        new_mask[cand] = True
-        left = ([c for c, _ in chans if not bool(new_mask[c])], [i for i, _ in layers if not new_flags[i]])
-        if left[0] or left[1]:
-            verdict['uncovered'] = True
-        widens = tuple(cand.tolist()) != tuple(plan.ext_key or ()) or new_flags != flags.tolist()
-        if not widens:
-            # nothing a plan can do about these offenders: the plan stays (no re-run, no new descriptor or graph); say so once per plan
-            seen = plan.info.get('uncovered', {'channels': [], 'layers': []})
-            new = [c for c in left[0] if c not in seen['channels']], [i for i in left[1] if i not in seen['layers']]
-            if update:                                            # (a read-only check does not touch the plan: it warns until an updating one records)
-                plan.info['uncovered'] = {'channels': sorted(seen['channels'] + new[0]), 'layers': sorted(seen['layers'] + new[1])}
-            if not (new[0] or new[1]):
-                verdict['message'] = msg + " (The plan cannot cover this: warned about once for this plan.)"
-                return verdict
-            msg += (" The plan cannot cover this (more than 64 massive channels, or large scores in a block without a q/k-pair form) and stays as it is; "
-                    "use precision 'exact' if 1e-3 must hold.  (Said once per plan.)")
-        elif update:
-            from esme.attention import HalfPlan
-            dev = self.embed_tokens.weight.device
-            sel = cand.to(torch.int32).contiguous().to(dev) if cand.numel() else None
-            info = dict(plan.info)
-            info['updates'] = info.get('updates', 0) + 1
-            info['massive_channels'] = int(cand.numel())
-            info['qk_pair_layers'] = sum(new_flags) if pair_ok else 0
-            info['uncovered'] = {'channels': sorted(left[0]), 'layers': sorted(left[1])}      # (already said below: not repeated for this plan)
-            self._half_plan = HalfPlan(sel, pair_ok and any(new_flags), info, qk_layers=new_flags if pair_ok else None, site_ref=plan.site_ref, qp=plan.qp)
-            self._drop_derived()
-            verdict['updated'] = True
-            msg += " The plan was widened (" + self._half_plan.describe() + "): re-run the batch."
-            if verdict.get('uncovered'):
-                msg += (" It cannot cover everything (more than 64 massive channels, or large scores in a block without a q/k-pair form): "
-                        "use precision 'exact' if 1e-3 must hold.")
-        verdict['message'] = msg
-        import warnings
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
-        return verdict
+    @property
+    def _half_guard(self):
+        """The HalfGuard of precision 'half' (read-only; None before the first 'half' forward or with half_guard off): `half_mode.guard`."""
+        return self.half_mode.guard
 
     def check_plan(self, update: bool = True):
         """Compare what the forwards in precision 'half' since the last call actually saw with what the plan assumed: a stream channel outside the
@@ -480,10 +233,8 @@ class ESM2(nn.Module):
         check reads the same bound.  A verdict no plan can cover (more than 64 massive channels; large scores in a block without a q/k-pair
         form) returns 'updated': False, 'uncovered': True and changes nothing -- no new plan, no new descriptor or graph, no re-run in
         predict_* -- and warns once per plan.  After editing weights in place, invalidate_graphs() drops the plan: the next forward recalibrates."""
-        vec = self._guard_snapshot()
-        if vec is None:
-            return None
-        return self._plan_verdict(vec.cpu(), update)              # the one synchronisation
+        vec = halfmode.guard_snapshot(self)
+        return None if vec is None else halfmode.plan_verdict(self, vec.cpu(), update)              # the one synchronisation
 
     def _apply(self, fn, *a, **kw):
         """`.to()`, `.cuda()`, dtype casts: the parameters' storage moves -- drop everything derived from it."""
@@ -501,7 +252,8 @@ class ESM2(nn.Module):
         pos, _ = _hip.seq_positions(cu_lens, total)
         rot = self.layers[0].self_attn.rot_emb if len(self.layers) else None
         cos = sin = None
-        plan = self.half_plan(device) if self.precision == 'half' else None
+        st = self.half_mode
+        plan, ovf, guard = st.for_forward(self, device) if self.precision == 'half' else (None, None, None)
         cos32 = sin32 = None
         if rot is not None:
             dt = {'exact': torch.float32, 'half': torch.float16}.get(self.precision, torch.bfloat16)
@@ -511,19 +263,8 @@ class ESM2(nn.Module):
         ctx = ForwardContext(pos, cos, sin, fold=self.fold_layernorm, exact_attn=self.precision == 'high',
                              f16=self.precision == 'half', plan=plan)
         ctx.cos32, ctx.sin32 = cos32, sin32
-        ctx.probe = getattr(self, '_calib_probe', None)
-        if self.precision == 'half':
-            ctx.ovf = self._overflow_flag(device)
-            ctx.guard = getattr(self, '_half_guard', None) if getattr(self, '_calib_probe', None) is not None else self._guard_buffers(device, plan)
+        ctx.probe, ctx.ovf, ctx.guard = st.probe, ovf, guard
         return ctx
-
-    # -- run-time range guard of precision 'half' --------------------------------------------------------------------
-    def _overflow_flag(self, device):
-        """int32 device flag the LayerNorm-folded GEMMs / the final LayerNorm set when a row's statistics are not finite."""
-        f = getattr(self, '_half_ovf', None)
-        if f is None or f.device != torch.device(device):
-            f = self._half_ovf = torch.zeros(1, dtype=torch.int32, device=device)
-        return f
 
     def check_overflow(self):
         """Raise OverflowError if a forward in precision 'half' since the last call saw a value leave IEEE fp16's range (|x| >= 65 504 in the
@@ -531,15 +272,7 @@ class ESM2(nn.Module):
         cleared.  predict_log_prob / predict_prob call it (their result is about to be read anyway); `model(...)` / `forward_representation`
         do not synchronise -- call it yourself before trusting their output, or read NaNs.  The bf16 modes ('fast', 'high', 'exact') have
         bf16's range (= fp32's) and nothing to check."""
-        f = getattr(self, '_half_ovf', None)
-        if f is None or torch.cuda.is_current_stream_capturing():
-            return self
-        if int(f.item()) != 0:
-            f.zero_()
-            raise OverflowError("precision='half': an activation left IEEE fp16's range (|x| >= 65 504) during a forward since the last check (this call's, "
-                                "or an earlier unchecked model(...) call's: the flag is sticky); the result holds inf / NaN.  Use precision 'exact' "
-                                "(bf16 pairs, fp32's range) for this checkpoint / input.")
-        return self
+        return halfmode.check_overflow(self)
 
     def _unpad(self, x, tokens):
         """Boolean-mask row gather: the `unpad_input` contract (esm.py:238)."""
@@ -603,49 +336,43 @@ class ESM2(nn.Module):
         ctx = self._context(cu_lens, max_len, x.shape[0], x.device)
         taps = []
         E = self.embed_dim
+
+        T, Ep, dev = *x.shape, x.device
+
+        def final_buffers(pair=None):              # 'exact' / 'half': the final LayerNorm's (hi, lo) bf16 pair (or the one given) and its fp32 output
+            alloc = torch.zeros if self.padded else torch.empty
+            return pair if pair is not None else alloc(T, 2 * Ep, dtype=torch.bfloat16, device=dev), alloc(T, Ep, dtype=torch.float32, device=dev)
+
+        def one_c_call(entry, x32, *half_args):    # 'exact' / 'half': all layers + the final LayerNorm through `entry` of esme.cforward
+            pair, rep32 = final_buffers()
+            entry(self, x32, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin, pair, rep32, *half_args)
+            return self._finish_representation(pair if want_pair else rep32, [], pad_output, pad_args, pad_indices, cu_lens, pad_width)
         if self.precision == 'exact':
             # split-operand mode: fp32 residual stream, activation pairs, fp32 results (esme.attention.FlashTransformerLayer.forward_exact).
             # Padded layouts (ESM2-35M): everything at the physical width, pad columns zero as in the other modes.
-            T, Ep = x.shape
             ctx.x32 = self._embedding_exact(x, tokens, pad_args, pad_indices)
             if self.c_forward and not layers and _hip.TRACE is None and self._c_forward_ok('exact'):
                 # all layers + the final LayerNorm through ONE C call (esme_hip_forward_exact: the launches below, bit-identical)
-                from esme import cforward
-                alloc = torch.zeros if self.padded else torch.empty
-                pair = alloc(T, 2 * Ep, dtype=torch.bfloat16, device=x.device)
-                x = alloc(T, Ep, dtype=torch.float32, device=x.device)
-                cforward.forward_layers_exact(self, ctx.x32, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin, pair, x)
-                if want_pair:
-                    x = pair
-                return self._finish_representation(x, [], pad_output, pad_args, pad_indices, cu_lens, pad_width)
+                from esme.cforward import forward_layers_exact
+                return one_c_call(forward_layers_exact, ctx.x32)
             ctx.order = _hip.seq_order(cu_lens)
             for i, layer in enumerate(self.layers):
                 layer.forward_exact(cu_lens, max_len, ctx)
                 if i in layers:
                     taps.append(ctx.x32.clone())
             ln = self.emb_layer_norm_after
-            alloc = torch.zeros if self.padded else torch.empty
-            pair = ctx.scratch.get('h')
-            pair = pair if pair is not None else alloc(T, 2 * Ep, dtype=torch.bfloat16, device=x.device)
-            x = alloc(T, Ep, dtype=torch.float32, device=x.device)
+            pair, x = final_buffers(ctx.scratch.get('h'))
             _hip.layernorm_split(ctx.x32, ln.weight, ln.bias, ln.eps, E, out=pair, out32=x, out_off=Ep)
             if want_pair:
                 x, taps = pair, []
         elif self.precision == 'half':
             # fp16 MFMA operands: x16 = fp16(stream) is what the LayerNorm-folded GEMMs read; the final LayerNorm and the LM head run in
             # the split-operand form (fp32 representation / logits)
-            T, Ep = x.shape
             x32 = self._embedding_exact(x, tokens, pad_args, pad_indices)
             if self.c_forward and not layers and _hip.TRACE is None and self._c_forward_ok('half'):
                 # all layers + the final LayerNorm through ONE C call (esme_hip_forward_half: the launches below, bit-identical)
-                from esme import cforward
-                alloc = torch.zeros if self.padded else torch.empty
-                pair = alloc(T, 2 * Ep, dtype=torch.bfloat16, device=x.device)
-                x = alloc(T, Ep, dtype=torch.float32, device=x.device)
-                cforward.forward_layers_half(self, x32, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin, pair, x, ctx.plan, ctx.ovf, ctx.cos32, ctx.sin32, ctx.guard)
-                if want_pair:
-                    x = pair
-                return self._finish_representation(x, [], pad_output, pad_args, pad_indices, cu_lens, pad_width)
+                from esme.cforward import forward_layers_half
+                return one_c_call(forward_layers_half, x32, ctx.plan, ctx.ovf, ctx.cos32, ctx.sin32, ctx.guard)
             # the stream as a float16 PAIR [hi | lo] (x = hi + lo: 22 significant bits): hi is the operand of the LayerNorm-folded GEMMs,
             # the residual GEMMs read and write the pair in place (8 B per element in whole lines; an fp32 stream + operand copy is 10).
             # Padded layouts (ESM2-35M): everything at the physical width, pad columns zero as in the fast mode.
@@ -667,9 +394,7 @@ class ESM2(nn.Module):
                     tap = _hip.pair_to_f32(ctx.xs, Ep)
                     taps.append(tap * scales[i + 1][1] if i < last else tap)          # the raw layer output: undo the stream's column scaling
             ln = self.emb_layer_norm_after
-            alloc = torch.zeros if self.padded else torch.empty
-            pair = alloc(T, 2 * Ep, dtype=torch.bfloat16, device=x.device)
-            x = alloc(T, Ep, dtype=torch.float32, device=x.device)
+            pair, x = final_buffers()
             _hip.layernorm_split(ctx.xs, ln.weight, ln.bias, ln.eps, E, out=pair, out32=x, in_off=Ep + ext, out_off=Ep, overflow_flag=ctx.ovf)
             if want_pair:
                 x, taps = pair, []
@@ -721,32 +446,14 @@ class ESM2(nn.Module):
                 return y.view(*pair.shape[:-1], y.shape[-1])
             return self.lm_head(self._forward_representation(tokens, pad_args, pad_output, pad_indices, [], lora_names=lora_names))
 
-    def _checked(self, run, tokens=None):
-        """Run `run()` (a forward ending in a softmax) and, in precision 'half' with half_check = 'sync', look at the range flag and the plan
-        guard (one synchronisation; the result is about to be read anyway).  A stale plan is widened and the batch re-run ONCE with it, so
-        the value returned rests on a plan that covers this very batch; an overflow raises.  (esme.pipeline reads both with each result
-        instead: `_defer_overflow`.)"""
-        y = run()
-        if self.precision == 'half' and self.half_check == 'sync' and tokens is not None and not getattr(self, '_defer_overflow', False):
-            self.check_tokens(tokens)
-        if self.precision != 'half' or self.half_check != 'sync' or getattr(self, '_defer_overflow', False) or torch.cuda.is_current_stream_capturing():
-            return y
-        self.check_overflow()
-        v = self.check_plan(update=True)
-        if v is not None and v['updated']:                    # (a verdict no plan can cover changes nothing: no re-run)
-            y = run()
-            self.check_overflow()
-            self.check_plan(update=False)                     # (whatever is left cannot be covered: warned about, not looped on)
-        return y
-
     def predict_log_prob(self, tokens, pad_args=None, pad_output=False, pad_indices=None, lora_names=None):
         with _hip.stream_scope(self.embed_tokens.weight.device):
-            return self._checked(lambda: _hip.softmax_rows(self(tokens, pad_args, pad_output, pad_indices, lora_names), log=True), tokens)
+            return halfmode.checked_run(self, lambda: _hip.softmax_rows(self(tokens, pad_args, pad_output, pad_indices, lora_names), log=True), tokens)
 
     def predict_prob(self, tokens, log=False, pad_args=None, pad_output=False, pad_indices=None,
                      lora_names=None):
         with _hip.stream_scope(self.embed_tokens.weight.device):
-            return self._checked(lambda: _hip.softmax_rows(self(tokens, pad_args, pad_output, pad_indices, lora_names), log=bool(log)), tokens)
+            return halfmode.checked_run(self, lambda: _hip.softmax_rows(self(tokens, pad_args, pad_output, pad_indices, lora_names), log=bool(log)), tokens)
 
     def graphed(self, tokens, pad_args, what: str = 'forward', clone: bool = True):
         """`getattr(self, what)(tokens, pad_args)` replayed from a hipGraph captured on first use of this
@@ -761,14 +468,11 @@ class ESM2(nn.Module):
         if getattr(self, '_graph_cache', None) is None:
             from esme.graph import GraphCache
             self._graph_cache = GraphCache(self)
-        y = self._graph_cache.run(what, tokens, pad_args, clone)        # (a capture warms up with the checks deferred: esme.graph)
-        if what == 'predict_log_prob' and self.precision == 'half' and self.half_check == 'sync' and not getattr(self, '_defer_overflow', False):
-            self.check_tokens(tokens)       # (as eager predict_log_prob does; the capture's warm-up runs with the checks deferred)
-            self.check_overflow()           # (once, after the replay: it sets the same sticky flags the eager call checks)
-            v = self.check_plan(update=True)
-            if v is not None and v['updated']:                    # (the widened plan dropped the captured graphs: this call captures anew)
-                y = self._graph_cache.run(what, tokens, pad_args, clone)
-        return y
+
+        def replay():                                      # (a capture warms up with the checks deferred: esme.graph)
+            return self._graph_cache.run(what, tokens, pad_args, clone)
+        # (as eager predict_log_prob does, once after the replay: it sets the same sticky flags; a widened plan dropped the captured graphs, so the re-run captures anew)
+        return halfmode.checked_run(self, replay, tokens, recheck=False) if what == 'predict_log_prob' else replay()
 
     def invalidate_graphs(self):
         """Forget captured hipGraphs, the C-entry model descriptor AND the calibrated HalfPlan of precision 'half' -- call it after changing
@@ -776,7 +480,7 @@ class ESM2(nn.Module):
         edited weights (a plan decided on the old ones would keep their massive channels and score bounds), and every derived weight copy
         (LN-folded, fp16, extension-tile, packed, padded) is rebuilt from them on next use."""
         from esme.nn import bump_weights_epoch
-        self._half_plan = None
+        self.half_mode.plan = None
         bump_weights_epoch()                  # every derived weight copy is rebuilt on next use (its key holds the epoch: esme.attention._version_key)
         self._drop_derived()
 

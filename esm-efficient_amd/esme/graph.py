@@ -23,7 +23,7 @@ from esme.nn import Derived, flatten_tensors
 # DERIVED device tensors (packed / LayerNorm-folded / padded weight copies, rotary tables) are allocated outside a graph's private pool and
 # read by the captured kernels through raw pointers.  The transformer block keeps its own in an esme.nn.Derived per module (found by type,
 # whatever it holds); these are the attributes under which the other modules cache theirs
-_DERIVED_ATTRS = ('_pad', '_embed_pad', '_cos_cached', '_sin_cached', '_half_ovf', '_table_cache')
+_DERIVED_ATTRS = ('_pad', '_embed_pad', '_cos_cached', '_sin_cached', '_table_cache')
 
 
 def external_tensors(model):
@@ -39,14 +39,7 @@ def external_tensors(model):
         for a in _DERIVED_ATTRS:
             keep.extend(flatten_tensors(getattr(m, a, None)))
     keep.extend(p.data for p in model.parameters())
-    plan = getattr(model, '_half_plan', None)             # precision 'half': the massive-channel list the extension K-tile kernels read
-    if plan is not None and getattr(plan, 'ext_sel', None) is not None:
-        keep.append(plan.ext_sel)
-    guard = getattr(model, '_half_guard', None)           # ... and the plan guard's device maxima / the range flag the captured kernels write
-    if guard is not None:
-        keep += [guard.col, guard.qk]
-    if getattr(model, '_half_ovf', None) is not None:
-        keep.append(model._half_ovf)
+    keep.extend(model.half_mode.tensors())                # precision 'half': the plan's channel list, the guard's maxima and the range flag the captured kernels read / write
     return keep
 
 
@@ -67,10 +60,7 @@ class GraphedForward:
         # stale plan seen by an earlier unchecked forward is still reported by the next check.  The inline checks of precision 'half'
         # (predict_log_prob's) are deferred meanwhile: a plan widened between warm-up and capture would clear this very entry from the
         # cache; the caller (ESM2.graphed) checks once after the first replay instead.
-        model = self.model
-        deferred = model.__dict__.get('_defer_overflow', None)
-        model._defer_overflow = True
-        try:
+        with self.model.half_mode.deferring():
             side = torch.cuda.Stream(device=self.tokens.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side), torch.no_grad():
@@ -81,12 +71,7 @@ class GraphedForward:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph), torch.no_grad():
                 self.out = self.fn(self.tokens, (self.cu_lens, self.max_len))
-        finally:
-            if deferred is None:
-                model.__dict__.pop('_defer_overflow', None)
-            else:
-                model._defer_overflow = deferred
-        self._keep = external_tensors(model)           # e.g. the rotary tables of THIS max_len survive a later regrow
+        self._keep = external_tensors(self.model)           # e.g. the rotary tables of THIS max_len survive a later regrow
         self.graph = graph
 
     def run(self, tokens: torch.Tensor, cu_lens: torch.Tensor, clone: bool = True) -> torch.Tensor:

@@ -18,6 +18,7 @@ from typing import Iterable, Iterator, Optional, Tuple
 
 import torch
 
+from esme import halfmode
 from esme.pooling import partition_mean_pool
 
 
@@ -75,31 +76,25 @@ class StreamedInference:
         # it inline.  Here the sticky device flag travels to the host WITH each result (4 bytes on the output stream, pinned) and is looked at
         # when the result is handed out: no extra synchronisation, and an activation that left fp16's range surfaces as OverflowError at the
         # first result that may carry it.
-        # The plan guard travels the same way (round 6): ESM2._guard_snapshot() judges the batch's device maxima against the plan ON the device, the
+        # The plan guard travels the same way (round 6): esme.halfmode.guard_snapshot() judges the batch's device maxima against the plan ON the device, the
         # few KB of the verdict vector ride to the host with the result, and a stale plan is widened when the first result computed under it is
         # handed out (RuntimeWarning naming the batch; later batches run covered; results already in flight are named too).
         guard = getattr(self.model, 'precision', None) == 'half'
         ring_flag = _PinnedRing(2 * self.depth + 2) if guard else None
         self._ring_plan = _PinnedRing(2 * self.depth + 2) if guard else None
-        deferred_before = getattr(self.model, '_defer_overflow', False)
-        if guard:
-            self.model._defer_overflow = True
-        try:
+        with self.model.half_mode.deferring(guard):
             yield from self._run(batches, dev, compute, copy_s, out_s, ring_in, ring_cu, ring_out, ring_flag, pending)
-        finally:
-            if guard:
-                self.model._defer_overflow = deferred_before
 
     def _hand_out(self, item, index):
         h, ev, flag_h, plan_h = item
         ev.synchronize()
         if plan_h is not None and float(plan_h[0]) != 0.0:
-            if self.model._plan_verdict(plan_h.clone(), update=True, where=f' (batch {index} of this stream)') is None:
+            if halfmode.plan_verdict(self.model, plan_h.clone(), update=True, where=f' (batch {index} of this stream)') is None:
                 import warnings                  # (an earlier batch's verdict has widened the plan meanwhile; THIS result still predates that)
                 warnings.warn(f"precision='half': batch {index} of this stream was computed under the plan an earlier batch showed to be stale (it has been "
                               "widened since); re-run it if the mode's 1e-3 must hold for it", RuntimeWarning, stacklevel=2)
         if flag_h is not None and int(flag_h[0]) != 0:
-            self.model._overflow_flag(self.device).zero_()
+            self.model.half_mode.overflow_flag(self.device).zero_()
             raise OverflowError(f"precision='half': an activation left IEEE fp16's range (|x| >= 65 504) by batch {index} of this stream; its result "
                                 "(and possibly the next batch's) holds inf / NaN.  Use precision 'exact' for this checkpoint / input.")
         return h
@@ -124,7 +119,7 @@ class StreamedInference:
                 if self.pool == 'mean':
                     out = partition_mean_pool(out, cu_d)
                 host = ring_out.take(out.shape, out.dtype)
-                snap = self.model._guard_snapshot() if ring_flag is not None else None      # (compute stream, before `computed`: judged against the plan this batch ran with)
+                snap = halfmode.guard_snapshot(self.model) if ring_flag is not None else None      # (compute stream, before `computed`: judged against the plan this batch ran with)
                 computed = torch.cuda.Event()
                 computed.record(compute)
                 flag_h = ring_flag.take((1,), torch.int32) if ring_flag is not None else None
@@ -134,7 +129,7 @@ class StreamedInference:
                     host.copy_(out, non_blocking=True)
                     out.record_stream(out_s)
                     if flag_h is not None:
-                        flag_h.copy_(self.model._overflow_flag(dev), non_blocking=True)
+                        flag_h.copy_(self.model.half_mode.overflow_flag(dev), non_blocking=True)
                     if plan_h is not None:
                         plan_h.copy_(snap, non_blocking=True)
                         snap.record_stream(out_s)

@@ -4,7 +4,7 @@ Round 5 decided the mode's robustness measures once, from 1 024 random residues 
 (`X`, `<unk>`, ESM-C's `<mask>`) or a live batch with larger scores than the calibration saw was invisible to it, and nothing at run time said so:
 a silent > 1e-3 by construction (profiles/r06_half_token_outlier_before.txt: 1.5e-3 ... 2.3e-3 with a clean bill of health).  Now
 
-  * the calibration batch holds every id of the alphabet (ESM2._calibration_batch) and may be extended by the caller's own data;
+  * the calibration batch holds every id of the alphabet (esme.halfmode.calibration_batch) and may be extended by the caller's own data;
   * the residual / projection epilogues keep running maxima of the two quantities the plan thresholds (esme_gemm_fusion_t.col_absmax / .qk_sumsq);
   * check_plan() / predict_* / StreamedInference compare them with the plan at their synchronisation points, widen it and say so.
 
@@ -204,8 +204,8 @@ def test_guard_catches_what_the_calibration_missed_and_the_widened_plan_holds():
     print(f'\n[guard] calibration on ids 4..23 only: first forward {first:.2e} (stale: {len(v["channels"])} channels, {len(v["layers"])} layers), re-run with {plan.describe()}: {second:.2e}')
     assert first > 1.2e-3 and second <= 1.0e-3, (first, second)
     # predict_log_prob from scratch: same model, fresh plan -> one warning, a covered result
-    model._half_plan = None
-    model._half_guard.clear()
+    model.half_mode.plan = None
+    model.half_mode.guard.clear()
     ref_lp = torch.log_softmax(ref.double(), dim=-1).float()
     with pytest.warns(RuntimeWarning, match='plan is stale'):
         lp = model.predict_log_prob(*args).float().cpu()
@@ -247,7 +247,7 @@ def test_guard_c_entry_equals_module_path_and_is_silent_on_benign_models():
     tokens, cu = sprinkled(lengths, [3, 24, 25, 26, 27, 28, 29, 30, 31, 32], 0.1)
     args = (tokens.to(DEV), (cu.to(DEV), max(lengths)))
     y1 = model(*args)
-    g = model._half_guard
+    g = model.half_mode.guard
     col1, qk1 = g.col.clone(), g.qk.clone()
     assert bool(col1.any()) and bool(qk1.any())
     g.clear()
@@ -272,12 +272,12 @@ def test_guard_c_entry_equals_module_path_and_is_silent_on_benign_models():
     tokens, cu = sprinkled(lengths, [3, 24, 32], 0.1)
     args = (tokens.to(DEV), (cu.to(DEV), max(lengths)))
     y1 = mc(*args)
-    qk1, col1 = mc._half_guard.qk.clone(), mc._half_guard.col.clone()
-    mc._half_guard.clear()
+    qk1, col1 = mc.half_mode.guard.qk.clone(), mc.half_mode.guard.col.clone()
+    mc.half_mode.guard.clear()
     mc.c_forward = False
     y2 = mc(*args)
     mc.c_forward = True
-    assert torch.equal(y1, y2) and bool(qk1.any()) and torch.equal(mc._half_guard.qk, qk1) and torch.equal(mc._half_guard.col, col1)
+    assert torch.equal(y1, y2) and bool(qk1.any()) and torch.equal(mc.half_mode.guard.qk, qk1) and torch.equal(mc.half_mode.guard.col, col1)
     with warnings.catch_warnings():
         warnings.simplefilter('error')
         assert mc.check_plan() is None
@@ -350,7 +350,7 @@ def test_user_calibration_batch_and_plan_kept_across_set_precision():
     m2._embedding_phys = lambda *a, **k: (_ for _ in ()).throw(RuntimeError('boom'))
     with pytest.raises(RuntimeError):
         m2.half_plan()
-    assert m2._half_plan is None and m2.precision == 'half'
+    assert m2.half_mode.plan is None and m2.precision == 'half'
     m2._embedding_phys = orig
     assert m2.half_plan().info['calibrated']
 

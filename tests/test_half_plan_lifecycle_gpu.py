@@ -18,6 +18,7 @@ import torch
 from oracle import esm_oracle as O
 from esme import _hip
 from esme import synthetic as syn
+from esme import halfmode
 from esme.attention import HalfPlan, _q_scale
 from test_attn_qp16_gpu import prescale, reference
 from test_half_guard_gpu import sprinkled, token_outlier_model
@@ -135,7 +136,7 @@ def _flip_qp(model):
 
 @pytest.mark.parametrize('case', ['esm2_qp', 'esmc', 'esm2_pairs'])
 def test_guard_bound_is_the_fed_q_k_bound_across_a_plan_change(case):
-    """_guard_measure's per-layer score bound equals a float64 recomputation from what each layer fed to attention; a guard filled under qp = True and
+    """guard_measure's per-layer score bound equals a float64 recomputation from what each layer fed to attention; a guard filled under qp = True and
     read after the plan switched to qp = False (and the other way round) reports the same bound, and forwards under the new plan merge into it."""
     lengths = [90, 33, 257]
     tokens, cu = syn.random_tokens(lengths, seed=6), syn.cu_lens_of(lengths)
@@ -159,9 +160,9 @@ def test_guard_bound_is_the_fed_q_k_bound_across_a_plan_change(case):
     # its bound matches the fed values to that rounding only; the projection epilogue measures exactly what it stores
     tol = 2e-4 if case == 'esmc' else 1e-5
     for flip in range(2):
-        model._half_guard.clear()
+        model.half_mode.guard.clear()
         fed = _fed_bounds(model, args)
-        _, bound, covered = model._guard_measure(model._half_guard, DEV)
+        _, bound, covered, _ = halfmode.guard_measure(model, model.half_mode.guard, DEV)
         bound, covered = bound.cpu().tolist(), covered.cpu().tolist()
         checked = [i for i, f in enumerate(fed) if f is not None and covered[i]]
         assert len(checked) == len(model.layers) - (1 if case == 'esm2_pairs' else 0), (fed, covered)
@@ -169,12 +170,12 @@ def test_guard_bound_is_the_fed_q_k_bound_across_a_plan_change(case):
             want = _bound(model, *fed[i])
             assert abs(bound[i] - want) <= tol * want, (case, flip, i, bound[i], want)
         _flip_qp(model)                                # (qp on -> off, then off -> on)
-        after = model._guard_measure(model._half_guard, DEV)[1].cpu().tolist()
+        after = halfmode.guard_measure(model, model.half_mode.guard, DEV)[1].cpu().tolist()
         for i in checked:
             assert abs(after[i] - bound[i]) <= 1e-6 * bound[i], (case, flip, i, after[i], bound[i])
         # a forward under the new plan merges into the same maxima: per head, the larger q norm of the two forwards times the larger k norm
         fed2 = _fed_bounds(model, args)
-        merged = model._guard_measure(model._half_guard, DEV)[1].cpu().tolist()
+        merged = halfmode.guard_measure(model, model.half_mode.guard, DEV)[1].cpu().tolist()
         for i in checked:
             want = _bound(model, torch.maximum(fed[i][0], fed2[i][0]), torch.maximum(fed[i][1], fed2[i][1]))
             assert abs(merged[i] - want) <= tol * want, (case, flip, i, merged[i], want)

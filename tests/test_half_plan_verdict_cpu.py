@@ -1,4 +1,4 @@
-"""precision 'half', host side of the plan's life cycle (no device): ESM2._plan_verdict on hand-made guard vectors and HalfPlans, the plan kept or
+"""precision 'half', host side of the plan's life cycle (no device): esme.halfmode.plan_verdict on hand-made guard vectors and HalfPlans, the plan kept or
 dropped by set_precision / invalidate_graphs, and the unit of the guard's q norms (HalfGuard.q_scaled).
 
 A verdict that no plan can cover (more than 64 massive channels; large scores in a block without a q/k-pair form: every ESM-C model) must leave
@@ -10,12 +10,13 @@ import warnings
 import pytest
 import torch
 
+from esme import halfmode
 from esme.attention import HalfGuard, HalfPlan
 from esme.esm import ESM2, ESMC
 
 
 def vec_of(model, ratio=None, bound=None, covered=None):
-    """A _guard_snapshot() as it arrives on the host: [stale, ratio (E), score bound (L), covered (L)]."""
+    """A guard_snapshot() as it arrives on the host: [stale, ratio (E), score bound (L), covered (L)]."""
     E, L = model.embed_dim, len(model.layers)
     ratio = torch.ones(E) if ratio is None else ratio
     bound = torch.zeros(L) if bound is None else bound
@@ -38,7 +39,7 @@ def sentinel(model):
 def verdicts(model, vec, n, update=True):
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter('always')
-        out = [model._plan_verdict(vec.clone(), update=update) for _ in range(n)]
+        out = [halfmode.plan_verdict(model, vec.clone(), update=update) for _ in range(n)]
     return out, [w for w in caught if issubclass(w.category, RuntimeWarning)]
 
 
@@ -141,10 +142,10 @@ def test_invalidate_graphs_recalibrates_and_set_precision_keeps_the_plan():
     assert model.half_plan() is plan and '_cdesc16' not in model.__dict__
     sentinel(model)
     model.invalidate_graphs()
-    assert getattr(model, '_half_plan', None) is None and '_cdesc16' not in model.__dict__
+    assert model.half_mode.plan is None and '_cdesc16' not in model.__dict__
     model.set_precision('half', robust=plan)
     model.load_state_dict(model.state_dict())
-    assert getattr(model, '_half_plan', None) is None
+    assert model.half_mode.plan is None
 
 
 def test_guard_q_norms_convert_between_units():

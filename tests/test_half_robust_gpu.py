@@ -325,7 +325,7 @@ def test_half_mode_range_guard_travels_with_streamed_results():
         direct = [getattr(model, what)(t.to(DEV), (c.to(DEV), m)).cpu() for t, (c, m) in batches]
         got = [h.clone() for h in StreamedInference(model, what, depth=2).run(iter(batches))]
         assert len(got) == len(direct) and all(torch.equal(a, b) for a, b in zip(got, direct))
-    assert not getattr(model, '_defer_overflow', False)
+    assert not model.half_mode.deferred
     with torch.no_grad():
         model.layers[1].final[3].bias.data[7] = 2.0e5
     model.invalidate_graphs()
@@ -333,9 +333,9 @@ def test_half_mode_range_guard_travels_with_streamed_results():
         with pytest.raises(OverflowError):
             for _ in StreamedInference(model, what, depth=2).run(iter(batches)):
                 pass
-        assert not getattr(model, '_defer_overflow', False)          # restored although the generator ended by an exception
+        assert not model.half_mode.deferred          # restored although the generator ended by an exception
         torch.cuda.synchronize()
-        model._overflow_flag(DEV).zero_()                               # (batches still in flight when the error surfaced set it again)
+        model.half_mode.overflow_flag(DEV).zero_()                               # (batches still in flight when the error surfaced set it again)
     with pytest.raises(OverflowError):                                  # the inline check is back
         model.predict_log_prob(batches[0][0].to(DEV), (batches[0][1][0].to(DEV), batches[0][1][1]))
     with torch.no_grad():

@@ -224,11 +224,12 @@ def test_calibration_batch_covers_the_vocabulary_and_plan_keys():
     its 8 sequences, is the same on every machine, and takes a caller's batch on board; HalfPlan keys derived weights on the channel LIST."""
     import torch
     from esme.esm import ESM2, ESMC
+    from esme import halfmode
     from esme.attention import HalfPlan, _ext_key
     for cls in (ESM2, ESMC):
         m = cls(num_layers=1, embed_dim=64, attention_heads=4)
-        tok, cu, max_len = m._calibration_batch()
-        tok2, _, _ = m._calibration_batch()
+        tok, cu, max_len = halfmode.calibration_batch(m)
+        tok2, _, _ = halfmode.calibration_batch(m)
         assert torch.equal(tok, tok2) and tok.numel() == 1024 and cu.tolist()[0] == 0 and cu.tolist()[-1] == 1024 and max_len == 192
         counts = torch.bincount(tok, minlength=33)
         al = m.alphabet
@@ -240,11 +241,11 @@ def test_calibration_batch_covers_the_vocabulary_and_plan_keys():
         starts = cu[:-1].long()
         assert (tok[starts] == al.cls_idx).all() and (tok[cu[1:].long() - 1] == al.eos_idx).all()
         m.HALF_CALIB_VOCAB = 'residues'
-        tr, _, _ = m._calibration_batch()
+        tr, _, _ = halfmode.calibration_batch(m)
         assert set(tr.tolist()) <= set(range(4, 24)) | {al.cls_idx, al.eos_idx}
         m.HALF_CALIB_VOCAB = 'all'
         m.set_precision('half', calib=(torch.tensor([0, 5, 24, 2, 0, 7, 2]), (torch.tensor([0, 4, 7], dtype=torch.int32), 4)))
-        tu, cuu, ml = m._calibration_batch()
+        tu, cuu, ml = halfmode.calibration_batch(m)
         assert tu.numel() == 1031 and cuu.tolist()[-3:] == [1024, 1028, 1031] and tu[-7:].tolist() == [0, 5, 24, 2, 0, 7, 2]
     a, b = torch.tensor([3, 9], dtype=torch.int32), torch.tensor([3, 10], dtype=torch.int32)
     pa, pb = HalfPlan(a), HalfPlan(b)
@@ -254,13 +255,13 @@ def test_calibration_batch_covers_the_vocabulary_and_plan_keys():
     assert not HalfPlan().qp and HalfPlan(qp=True).qp and 'fixed-reference' in HalfPlan(qp=True).describe() and 'fixed-reference' not in pa.describe()
     assert ESM2.HALF_QP_BOUND < ESM2.HALF_SCORE_BOUND and isinstance(ESM2.half_qp, bool)
     m = ESM2(num_layers=2, embed_dim=64, attention_heads=4)
-    m._half_plan = HalfPlan(qp=True, info={'calibrated': True}, qk_layers=[False, False])
+    m.half_mode.plan = HalfPlan(qp=True, info={'calibrated': True}, qk_layers=[False, False])
     m.precision = 'half'
     vec = torch.zeros(1 + 64 + 2 + 2)
     vec[0], vec[1 + 3], vec[1 + 64 + 2:] = 1.0, 50.0, 1.0            # a stale verdict: channel 3 at 50 x the median
     with pytest.warns(RuntimeWarning):
-        v = m._plan_verdict(vec, update=True)
-    assert v['updated'] and m._half_plan.qp and m._half_plan.ext_key == (3,)         # widening the plan keeps the attention form
+        v = halfmode.plan_verdict(m, vec, update=True)
+    assert v['updated'] and m.half_mode.plan.qp and m.half_mode.plan.ext_key == (3,)         # widening the plan keeps the attention form
 
 
 def test_no_cpu_fallback_and_missing_library(monkeypatch):

@@ -1,11 +1,11 @@
 #!/usr/bin/env python
-"""What ESM2._guard_snapshot() (the device-side half of the plan guard's verdict, taken once per streamed batch) costs: GPU time and host time."""
+"""What esme.halfmode.guard_snapshot() (the device-side half of the plan guard's verdict, taken once per streamed batch) costs: GPU time and host time."""
 import os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, 'esm-efficient_amd')):
     sys.path.insert(0, p)
 import torch
-from esme import ESM, synthetic as syn
+from esme import ESM, halfmode, synthetic as syn
 kind, L, E, H = syn.MODEL_ZOO['esm2_650m']
 with tempfile.TemporaryDirectory() as td:
     path = syn.write_checkpoint(os.path.join(td, 'm.safetensors'), 'esm2_650m', L, E, H, seed=0)
@@ -20,6 +20,6 @@ with torch.no_grad():
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter(); s.record()
         for _ in range(20):
-            v = model._guard_snapshot()
+            v = halfmode.guard_snapshot(model)
         e.record(); t1 = time.perf_counter(); torch.cuda.synchronize()
-        print(f'_guard_snapshot: host {1e3 * (t1 - t0) / 20:.3f} ms per call, GPU {s.elapsed_time(e) / 20:.3f} ms per call, vector {None if v is None else tuple(v.shape)}')
+        print(f'guard_snapshot: host {1e3 * (t1 - t0) / 20:.3f} ms per call, GPU {s.elapsed_time(e) / 20:.3f} ms per call, vector {None if v is None else tuple(v.shape)}')
