@@ -1,0 +1,373 @@
+// Residue-contact logits from the attention maps of one layer, reduced as they are produced (include/esme_hip_contacts.h).
+//
+// Per sequence (S rows, f / e rows trimmed at the ends, n = S - f - e) and head h:
+//     P = softmax_j(q_i . k_j * scale) over all S keys,  A = P[f : S - e, f : S - e],  Y = A + A^T,  r = Y 1,  t = 1^T r,
+//     map += sum_h w_h (Y - r r^T / t).
+// Everything but r r^T / t is linear in P, so no S x S object is ever stored: four launches per layer, each a sweep of
+// 64 x 64 score tiles on v_mfma_f32_16x16x32_bf16 (fp32 accumulators, softmax in fp32 log2 units, P never rounded):
+//  - contact_stats_kernel   per (sequence, head, 64 query rows): all key tiles twice -> row maximum m, row sum l, and the
+//                           row sum of A (the sum over the kept keys only, times 1 / l);
+//  - contact_colsum_kernel  per (sequence, head, 64 key rows): all kept query tiles, P normalised with their m, l -> column sums
+//                           of A; r = row sum + column sum;
+//  - contact_total_kernel   per (sequence, head): t = sum_i r_i, lane-strided partial sums and one butterfly (a fixed order);
+//  - contact_pair_kernel    per (sequence, tile pair I <= J), heads in index order: S_IJ = Q_I K_J^T and S_JI^T = K_I Q_J^T land in
+//                           the same register layout, acc += w_h (A_IJ + A_JI^T) - (w_h / t_h) r_I r_J^T; the tile and its mirror
+//                           image are stored (or added to the map) from the same registers: the map is exactly symmetric.
+// A wave owns 16 rows of its tile (fragments straight from global memory, 16 bytes per lane) against the 64 rows of the streamed
+// tile, which the workgroup stages in LDS once (row pitch D + 8 elements: the 16-byte fragment reads of 16 consecutive rows fall on
+// distinct bank groups).  In the accumulator of one MFMA lane (c = lane & 15, g = lane >> 4) holds rows 4 g + 0..3 of column c.
+// Every index is relative to the sequence's own first row and every reduction has a fixed order: a sequence's map does not
+// depend on its neighbours (bit-identical alone and packed, run to run).  No atomics.
+#include "common.h"
+#include "launch.h"
+#include "../../include/esme_hip_contacts.h"
+
+namespace esme {
+
+static constexpr int kCT = 64;            // tile edge: rows of a workgroup's own tile and of the streamed tile
+static constexpr int kContactMaxZ = 65535;
+
+struct ContactArgs {
+    const u16* q; const u16* k; int64_t ld;
+    const int32_t* cu; int b0; int B; int64_t T; int H;
+    float cs;                             // softmax_scale * log2(e), or 1 with a prescaled q
+    int f, e;                             // rows trimmed at the front / back of every sequence
+    float* ws_m; float* ws_l; float* ws_r; float* ws_t;
+    const float* w; float bias; int init; float* map; const int64_t* map_off;
+};
+
+template <int D> struct ContactDims {
+    static constexpr int DS = D <= 32 ? 1 : D / 32;     // MFMA k-steps (head dim 16: the upper half of the one step is zero)
+    static constexpr int LD = D + 8;                    // LDS row pitch in elements
+};
+
+__device__ __forceinline__ bf16x8 zero_frag() { return __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u}); }
+
+// operand fragment of row `row`: elements 32 ks + 8 g .. + 7 (A and B operands of the 16x16x32 MFMA share this map)
+template <int D>
+__device__ __forceinline__ bf16x8 global_frag(const u16* base, unsigned int ld, int row, int ks, int g) {
+    if (D == 16 && g >= 2) return zero_frag();
+    return *reinterpret_cast<const bf16x8*>(base + ((unsigned int)row * ld + (unsigned int)(ks * 32 + g * 8)));
+}
+template <int D>
+__device__ __forceinline__ bf16x8 lds_frag(const u16* tile, int row, int ks, int g) {
+    if (D == 16 && g >= 2) return zero_frag();
+    return *reinterpret_cast<const bf16x8*>(tile + row * ContactDims<D>::LD + ks * 32 + g * 8);
+}
+
+// rows row0 .. row0 + 63 of one head's (S, D) operand into LDS; rows past the sequence repeat its last row (their scores are masked)
+template <int D>
+__device__ __forceinline__ void stage_tile(u16* tile, const u16* base, unsigned int ld, int row0, int S) {
+    constexpr int CPR = D / 8, NCH = kCT * CPR;
+    for (int ch = threadIdx.x; ch < NCH; ch += 256) {
+        const int row = ch / CPR, col = (ch % CPR) * 8;
+        int gr = row0 + row;
+        gr = gr < S ? gr : S - 1;
+        *reinterpret_cast<u32x4*>(tile + row * ContactDims<D>::LD + col) =
+            *reinterpret_cast<const u32x4*>(base + ((unsigned int)gr * ld + (unsigned int)col));
+    }
+}
+
+// s[cb][r] = (own row 4 g + r) . (tile row 16 cb + c)
+template <int D>
+__device__ __forceinline__ void score_tile(const bf16x8* a, const u16* tile, int c, int g, f32x4* s) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+        s[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < ContactDims<D>::DS; ++ks) s[cb] = mfma_16x16x32<false>(a[ks], lds_frag<D>(tile, cb * 16 + c, ks, g), s[cb]);
+    }
+}
+
+// over the 16 lanes that hold one accumulator row (lane bits 0..3), a fixed butterfly
+__device__ __forceinline__ float row16_max(float v) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float row16_sum(float v) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void contact_stats_kernel(const ContactArgs a) {
+    constexpr int DS = ContactDims<D>::DS;
+    __shared__ __attribute__((aligned(16))) u16 tile[kCT * ContactDims<D>::LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const int b = a.b0 + blockIdx.z, h = blockIdx.y;
+    const int s0 = a.cu[b], S = a.cu[b + 1] - s0, n = S - a.f - a.e;
+    const int I0 = blockIdx.x * kCT;
+    if (n <= 0 || I0 >= n) return;                                          // (block-uniform)
+    const unsigned int ld = (unsigned int)a.ld;
+    const u16* qb = a.q + (int64_t)s0 * a.ld + h * D;
+    const u16* kb = a.k + (int64_t)s0 * a.ld + h * D;
+    int qi = I0 + wave * 16 + c;
+    qi = qi < n ? qi : n - 1;
+    bf16x8 af[DS];
+#pragma unroll
+    for (int ks = 0; ks < DS; ++ks) af[ks] = global_frag<D>(qb, ld, a.f + qi, ks, g);
+
+    f32x4 s[4];
+    float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int kt = 0; kt < S; kt += kCT) {
+        __syncthreads();
+        stage_tile<D>(tile, kb, ld, kt, S);
+        __syncthreads();
+        score_tile<D>(af, tile, c, g, s);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            if (kt + cb * 16 + c < S) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], s[cb][r] * a.cs);                    // [score-scale]
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mx[r] = row16_max(mx[r]);
+
+    float ls[4] = {0.f, 0.f, 0.f, 0.f}, lt[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < S; kt += kCT) {
+        __syncthreads();
+        stage_tile<D>(tile, kb, ld, kt, S);
+        __syncthreads();
+        score_tile<D>(af, tile, c, g, s);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            const int key = kt + cb * 16 + c;
+            const bool kept = key >= a.f && key < S - a.e;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = key < S ? exp2f(s[cb][r] * a.cs - mx[r]) : 0.f;                       // [exp]
+                ls[r] += p;                                                                           // [row-sum]
+                lt[r] += kept ? p : 0.f;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        ls[r] = row16_sum(ls[r]);
+        lt[r] = row16_sum(lt[r]);
+    }
+    if (c == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = I0 + wave * 16 + 4 * g + r;
+            if (row < n) {
+                const int64_t idx = (int64_t)h * a.T + s0 + a.f + row;
+                a.ws_m[idx] = mx[r];
+                a.ws_l[idx] = ls[r];
+                a.ws_r[idx] = lt[r] * (1.0f / ls[r]);                                                 // [inv-l] [normalise]
+            }
+        }
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void contact_colsum_kernel(const ContactArgs a) {
+    constexpr int DS = ContactDims<D>::DS;
+    __shared__ __attribute__((aligned(16))) u16 tile[kCT * ContactDims<D>::LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const int b = a.b0 + blockIdx.z, h = blockIdx.y;
+    const int s0 = a.cu[b], S = a.cu[b + 1] - s0, n = S - a.f - a.e;
+    const int I0 = blockIdx.x * kCT;
+    if (n <= 0 || I0 >= n) return;                                          // (block-uniform)
+    const unsigned int ld = (unsigned int)a.ld;
+    const u16* qb = a.q + (int64_t)s0 * a.ld + h * D;
+    const u16* kb = a.k + (int64_t)s0 * a.ld + h * D;
+    const int64_t st = (int64_t)h * a.T + s0 + a.f;                        // statistics of this (head, sequence): kept row i at st + i
+    int kj = I0 + wave * 16 + c;
+    kj = kj < n ? kj : n - 1;
+    bf16x8 af[DS];
+#pragma unroll
+    for (int ks = 0; ks < DS; ++ks) af[ks] = global_frag<D>(kb, ld, a.f + kj, ks, g);
+
+    f32x4 s[4];
+    float col[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int qt = 0; qt < n; qt += kCT) {
+        __syncthreads();
+        stage_tile<D>(tile, qb, ld, a.f + qt, S);
+        __syncthreads();
+        score_tile<D>(af, tile, c, g, s);                                   // s[cb][r] = k (own row 4 g + r) . q (row qt + 16 cb + c)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            const int qi = qt + cb * 16 + c;
+            const bool valid = qi < n;
+            const int64_t qs = st + (valid ? qi : n - 1);
+            const float m = a.ws_m[qs], inv = 1.0f / a.ws_l[qs];                                      // [inv-l]
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = exp2f(s[cb][r] * a.cs - m) * inv;                                     // [exp] [normalise]
+                col[r] += valid ? p : 0.f;                                                            // [col-sum]
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) col[r] = row16_sum(col[r]);
+    if (c == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = I0 + wave * 16 + 4 * g + r;
+            if (row < n) a.ws_r[st + row] = a.ws_r[st + row] + col[r];                                // [r]
+        }
+    }
+}
+
+// t = sum_i r_i: lane l sums rows l, l + 64, ... in order, then one butterfly.  Grid (H, sequences), one wave.
+__global__ __launch_bounds__(64) void contact_total_kernel(const ContactArgs a) {
+    const int b = a.b0 + blockIdx.y, h = blockIdx.x;
+    const int s0 = a.cu[b], n = a.cu[b + 1] - s0 - a.f - a.e;
+    if (n <= 0) return;
+    const float* r = a.ws_r + (int64_t)h * a.T + s0 + a.f;
+    float v = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) v += r[i];                                              // [t]
+    v = wave_sum(v);
+    if (threadIdx.x == 0) a.ws_t[(int64_t)h * a.B + b] = v;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void contact_pair_kernel(const ContactArgs a) {
+    constexpr int DS = ContactDims<D>::DS;
+    __shared__ __attribute__((aligned(16))) u16 tk[kCT * ContactDims<D>::LD];
+    __shared__ __attribute__((aligned(16))) u16 tq[kCT * ContactDims<D>::LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const int b = a.b0 + blockIdx.z;
+    const int s0 = a.cu[b], S = a.cu[b + 1] - s0, n = S - a.f - a.e;
+    if (n <= 0) return;                                                     // (block-uniform)
+    // tile pair p -> (I, J), I <= J: J is the largest integer with J (J + 1) / 2 <= p
+    const long long p = blockIdx.x;
+    long long J = (long long)((sqrt((double)(8 * p + 1)) - 1.0) * 0.5);
+    while ((J + 1) * (J + 2) / 2 <= p) ++J;
+    while (J * (J + 1) / 2 > p) --J;
+    const long long I = p - J * (J + 1) / 2;
+    if (J * kCT >= n) return;                                               // (block-uniform)
+    const int I0 = (int)I * kCT, J0 = (int)J * kCT;
+    const unsigned int ld = (unsigned int)a.ld;
+    int ri = I0 + wave * 16 + c;                                            // own operand row (fragment map: row on lane bits 0..3)
+    ri = ri < n ? ri : n - 1;
+    int si[4];                                                              // own accumulator rows
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        si[r] = I0 + wave * 16 + 4 * g + r;
+        si[r] = si[r] < n ? si[r] : n - 1;
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[cb][r] = 0.f;
+
+    for (int h = 0; h < a.H; ++h) {                                         // heads in index order
+        const u16* qb = a.q + (int64_t)s0 * a.ld + h * D;
+        const u16* kb = a.k + (int64_t)s0 * a.ld + h * D;
+        const int64_t st = (int64_t)h * a.T + s0 + a.f;
+        __syncthreads();
+        stage_tile<D>(tk, kb, ld, a.f + J0, S);
+        stage_tile<D>(tq, qb, ld, a.f + J0, S);
+        __syncthreads();
+        bf16x8 aq[DS], ak[DS];
+#pragma unroll
+        for (int ks = 0; ks < DS; ++ks) {
+            aq[ks] = global_frag<D>(qb, ld, a.f + ri, ks, g);
+            ak[ks] = global_frag<D>(kb, ld, a.f + ri, ks, g);
+        }
+        float mi[4], ii[4], rr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            mi[r] = a.ws_m[st + si[r]];
+            ii[r] = 1.0f / a.ws_l[st + si[r]];                                                        // [inv-l]
+            rr[r] = a.ws_r[st + si[r]];
+        }
+        const float wh = a.w[h];
+        const float u = wh / a.ws_t[(int64_t)h * a.B + b];                                            // [w-over-t]
+        f32x4 s1[4], s2[4];
+        score_tile<D>(aq, tk, c, g, s1);                                    // s1[cb][r] = q_i . k_j,  i = own row 4 g + r, j = J0 + 16 cb + c
+        score_tile<D>(ak, tq, c, g, s2);                                    // s2[cb][r] = k_i . q_j = the score of (j, i)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+            int sj = J0 + cb * 16 + c;
+            sj = sj < n ? sj : n - 1;
+            const float mj = a.ws_m[st + sj], ij = 1.0f / a.ws_l[st + sj], rj = a.ws_r[st + sj];     // [inv-l]
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p1 = exp2f(s1[cb][r] * a.cs - mi[r]) * ii[r];                             // [exp] [normalise]  A_ij
+                const float p2 = exp2f(s2[cb][r] * a.cs - mj) * ij;                                   // [exp] [normalise]  A_ji
+                acc[cb][r] = fmaf(wh, p1 + p2, acc[cb][r]);                                           // [sym] [head-sum]
+                acc[cb][r] = fmaf(-u, rr[r] * rj, acc[cb][r]);                                        // [apc] [head-sum]
+            }
+        }
+    }
+
+    float* mo = a.map + a.map_off[b];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+        const int j = J0 + cb * 16 + c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = I0 + wave * 16 + 4 * g + r;
+            if (i < n && j < n && (I != J || i <= j)) {                     // the diagonal tile: its upper triangle, mirrored
+                const int64_t up = (int64_t)i * n + j, lo = (int64_t)j * n + i;
+                const float v = a.init ? a.bias + acc[cb][r] : mo[up] + acc[cb][r];                   // [layer-sum]
+                mo[up] = v;
+                if (i != j) mo[lo] = v;
+            }
+        }
+    }
+}
+
+template <int D>
+static int launch_contacts(const ContactArgs& a0, int nt, int64_t npairs, hipStream_t s) {
+    return for_sequence_chunks(a0.B, kContactMaxZ, [&](int b0, int nb) {
+        ContactArgs a = a0;
+        a.b0 = b0;
+        const dim3 tiles((unsigned int)nt, (unsigned int)a.H, (unsigned int)nb);
+        hipLaunchKernelGGL(contact_stats_kernel<D>, tiles, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(contact_colsum_kernel<D>, tiles, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(contact_total_kernel, dim3((unsigned int)a.H, (unsigned int)nb), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(contact_pair_kernel<D>, dim3((unsigned int)npairs, 1u, (unsigned int)nb), dim3(256), 0, s, a);
+        return check_launch("contact_layer");
+    });
+}
+
+}  // namespace esme
+
+using namespace esme;
+
+extern "C" int64_t esme_hip_contact_workspace_bytes(int B, int64_t T, int H) {
+    ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0, "contact_workspace_bytes: bad sizes");
+    return (3 * (int64_t)H * T + (int64_t)H * B) * (int64_t)sizeof(float);
+}
+
+extern "C" int esme_hip_contact_layer(const void* q, const void* k, int64_t ld_qk, const int32_t* cu_lens, int B, int64_t T, int H,
+                                      int d, int max_len, float softmax_scale, int q_prescaled, int trim_front, int trim_back,
+                                      const float* w, float bias, int init, float* map, const int64_t* map_off, void* workspace,
+                                      int64_t ws_bytes, void* stream) {
+    ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0 && trim_front >= 0 && trim_back >= 0, "contact_layer: bad sizes");
+    if (B == 0 || T == 0) return ESME_OK;
+    ESME_CHECK_ARG(q && k && cu_lens && w && map && map_off && workspace, "contact_layer: null pointer");
+    ESME_CHECK_ARG(ld_qk % 8 == 0 && ld_qk >= (int64_t)H * d, "contact_layer: bad row stride");
+    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(workspace) && (reinterpret_cast<uintptr_t>(map) & 3u) == 0, "contact_layer: misaligned");
+    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && T < 0x80000000LL, "contact_layer: max_len must be > 0, H <= 65535, T < 2^31");
+    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_layer: head dim must be 16, 32, 64 or 128");
+    if ((int64_t)max_len * ld_qk >= ESME_HIP_CONTACT_MAX_SEQ_ELEMS)
+        ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_layer: max_len * ld_qk passes 2^32 elements (ESME_HIP_CONTACT_MAX_SEQ_ELEMS)");
+    const int64_t need = esme_hip_contact_workspace_bytes(B, T, H);
+    ESME_CHECK_ARG(ws_bytes >= need, "contact_layer: workspace too small (see esme_hip_contact_workspace_bytes)");
+    const int64_t nmax = (int64_t)max_len - trim_front - trim_back;
+    if (nmax <= 0) return ESME_OK;                                          // every sequence is trimmed away
+    const int64_t nt = (nmax + kCT - 1) / kCT, npairs = nt * (nt + 1) / 2;
+    if (npairs > 0x7fffffffLL) ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_layer: too many tile pairs");
+    float* ws = (float*)workspace;
+    const int64_t HT = (int64_t)H * T;
+    ContactArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, B, T, H,
+                  q_prescaled ? 1.0f : softmax_scale * 1.4426950408889634f, trim_front, trim_back,
+                  ws, ws + HT, ws + 2 * HT, ws + 3 * HT, w, bias, init, map, map_off};
+    const hipStream_t s = (hipStream_t)stream;
+    switch (d) {
+        case 16: return launch_contacts<16>(a, (int)nt, npairs, s);
+        case 32: return launch_contacts<32>(a, (int)nt, npairs, s);
+        case 64: return launch_contacts<64>(a, (int)nt, npairs, s);
+        default: return launch_contacts<128>(a, (int)nt, npairs, s);
+    }
+}

@@ -12,6 +12,8 @@ that is not on a HIP device raises (there is no CPU fallback).
 `quantization='4bit'` / `'8bit'` keep the layer projections 4-bit / int8 in HBM (esme/quantization.py).
 ESM-1b / ESM-1v (learned positions, no rotary) run on the same kernels (`ESM1b`, `ESM1v`).
 LoRA adapters (`add_lora` / `load_lora` / `save_lora`, `lora_names=`) run for inference in precision 'fast' (esme/lora.py).
+`predict_contacts` (with `set_contact_head`) reduces the attention maps into contact maps layer by layer (esme/contacts.py); the
+reference has no counterpart (flash-attn returns no attention weights).
 Out of scope here: training (no backward), int8-activation matmuls,
 activation checkpointing (training only), hub download (no network).
 """
@@ -102,6 +104,7 @@ class ESM2(nn.Module):
         self.checkpointing = False
         self.embed_scale = 1
         self.half_mode = halfmode.HalfState()      # precision 'half': plan, guard, range flag (esme.halfmode)
+        self.contact_head = None                   # esme.contacts.ContactHead once set_contact_head() / from_pretrained() found one
         self.embed_tokens = nn.Embedding(self.vocab_size, embed_dim, dtype=dtype,
                                          padding_idx=self.alphabet.padding_idx)
         self.embed_tokens.weight.requires_grad_(False)
@@ -314,9 +317,11 @@ class ESM2(nn.Module):
                 x = torch.cat([x[..., i * Ep:i * Ep + E] for i in range(x.shape[-1] // Ep)], dim=-1)
             return x
 
-    def _forward_representation(self, tokens, pad_args, pad_output, pad_indices, layers, want_pair=False, lora_names=None):
+    def _forward_representation(self, tokens, pad_args, pad_output, pad_indices, layers, want_pair=False, lora_names=None, contacts=None):
         """forward_representation at the PHYSICAL width (== the logical one unless the layout is padded).  `want_pair`
-        (precision 'exact' only): return the (hi, lo) bf16 pair of the final-LayerNorm output, the LM head's operand."""
+        (precision 'exact' only): return the (hi, lo) bf16 pair of the final-LayerNorm output, the LM head's operand.
+        `contacts` (predict_contacts, precision 'fast'): called with (cu_lens, max_len), returns the ContactAccumulator that every
+        attention block hands its (q, k) to; the layers then run through the per-layer module loop, as with `layers=[...]`."""
         lora = self._lora_select(lora_names)                   # None without adapters; else the names this call applies
         x = self._embedding_phys(tokens, pad_args)
         if pad_args is not None:
@@ -334,6 +339,8 @@ class ESM2(nn.Module):
         # its pad_input raises an index error) -- using S keeps the scatter in bounds for fixed-width batches too.
         pad_width = tokens.shape[1] if pad_args is None else max_len
         ctx = self._context(cu_lens, max_len, x.shape[0], x.device)
+        if contacts is not None:
+            ctx.contacts = contacts(cu_lens, max_len)
         taps = []
         E = self.embed_dim
 
@@ -410,7 +417,7 @@ class ESM2(nn.Module):
                     taps.append(x.clone())
             ln = self.emb_layer_norm_after
             _hip.layernorm_f32(ctx.x32[:, :E], ln.weight, ln.bias, ln.eps, out=x[:, :E])
-        elif self.c_forward and not layers and _hip.TRACE is None and self._c_forward_ok():
+        elif self.c_forward and not layers and ctx.contacts is None and _hip.TRACE is None and self._c_forward_ok():
             from esme import cforward
             cforward.forward_layers(self, x, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin)
         else:
@@ -455,12 +462,65 @@ class ESM2(nn.Module):
         with _hip.stream_scope(self.embed_tokens.weight.device):
             return halfmode.checked_run(self, lambda: _hip.softmax_rows(self(tokens, pad_args, pad_output, pad_indices, lora_names), log=bool(log)), tokens)
 
+    # -- contact prediction (esme/contacts.py) -----------------------------------------
+    def set_contact_head(self, head):
+        """Install the contact regression: a ContactHead, or anything ContactHead.load accepts (a safetensors / torch file, a state
+        dict).  ValueError unless it has num_layers * attention_heads features.  ESM-C ships no contact regression: supply your own."""
+        from esme.contacts import ContactHead
+        L, H = len(self.layers), self.attention_heads
+        if not isinstance(head, ContactHead):
+            head = ContactHead.load(head)
+        n = head.regression.weight.numel()
+        if n != L * H:
+            raise ValueError(f'contact head with {n} features does not fit a model with {L} layers x {H} heads = {L * H}')
+        if (head.num_layers, head.attention_heads) != (L, H):
+            fitted = ContactHead(L, H, head.prepend_bos, head.append_eos)
+            fitted.regression.weight.data.copy_(head.regression.weight.data.reshape(1, -1))
+            fitted.regression.bias.data.copy_(head.regression.bias.data.reshape(1))
+            head = fitted
+        self.contact_head = head.to(device=self.embed_tokens.weight.device, dtype=torch.float32)
+        return self
+
+    def predict_contacts(self, tokens, pad_args=None, pad_output=False, logits=False, lora_names=None, _keep_qk=False):
+        """Contact probabilities (`logits=True`: the logits) between the residues of every protein, float32.  Packed input
+        (`pad_args=(cu_lens, max_len)`): a list of B (n_s, n_s) views of one buffer, n_s = the sequence's length without bos / eos; 2-D
+        tokens or `pad_output=True`: (B, S - f - e, S - f - e) with zeros outside each protein's block.  Runs the forward in precision
+        'fast' with one extra kernel call per layer (esme_hip_contact_layer); no attention map is stored."""
+        if self.contact_head is None:
+            raise RuntimeError('predict_contacts: the model has no contact head (model.set_contact_head(head or path); ESM-C ships none)')
+        if self.precision != 'fast':
+            raise NotImplementedError(f"predict_contacts runs in precision 'fast' only; precision {self.precision!r} is not implemented "
+                                      "(set_precision('fast'))")
+        from esme.contacts import ContactAccumulator
+        head, box = self.contact_head, []
+
+        def make(cu_lens, max_len):
+            box.append(ContactAccumulator(head, cu_lens, max_len, self.attention_heads, self.head_pad,
+                                          self.embed_dim // self.attention_heads, keep_qk=_keep_qk))
+            return box[0]
+        with _hip.stream_scope(self.embed_tokens.weight.device):
+            self._forward_representation(tokens, pad_args, False, None, [], lora_names=lora_names, contacts=make)
+            acc = box[0]
+            maps = acc.result(len(self.layers), logits)
+            if _keep_qk:
+                self._contact_qk = acc.qk
+            if not (pad_output or pad_args is None):
+                return maps
+            f, e = head.trim
+            width = (tokens.shape[1] if pad_args is None else acc.max_len) - f - e
+            out = torch.zeros(len(maps), max(width, 0), max(width, 0), dtype=torch.float32, device=acc.out.device)
+            for i, m in enumerate(maps):
+                out[i, :m.shape[0], :m.shape[1]] = m
+            return out
+
     def graphed(self, tokens, pad_args, what: str = 'forward', clone: bool = True):
         """`getattr(self, what)(tokens, pad_args)` replayed from a hipGraph captured on first use of this
         input shape (esme/graph.py).  For repeated shapes of small batches, where ~160 Python-issued launches
         cost more than the GPU work.  With `clone=False` the result is a static buffer that the next replay of
         the same shape overwrites.  'predict_log_prob' in precision 'half' with half_check = 'sync' checks the token ids, the range flag and the
         plan after each replay, as the eager call does (a widened plan is re-captured and replayed once)."""
+        if what == 'predict_contacts':
+            raise NotImplementedError('graphed(): hipGraph replay of predict_contacts is not implemented; call model.predict_contacts directly')
         assert what in ('forward', 'forward_representation', 'predict_log_prob')
         if self.has_lora:
             raise NotImplementedError('graphed(): hipGraph replay is not implemented for a model with LoRA adapters (a graph bakes one adapter '
@@ -646,7 +706,10 @@ class ESM2(nn.Module):
         model = cls.create_model(path, checkpointing=checkpointing)
         dev = torch.device('cuda', device) if isinstance(device, int) else torch.device(device)
         state = load_file(path, device=str(dev))
+        contact = {k: state.pop(k) for k in [k for k in state if k.startswith('contact_head.')]}
         model.load_state_dict(state, strict=True, assign=True)
+        if any(k.endswith('regression.weight') for k in contact):      # the checkpoint carries a contact regression
+            model.set_contact_head(contact)
         for p in model.parameters():
             p.requires_grad_(False)
         if quantization is not None:                    # weight-only storage formats (esme/quantization.py)
