@@ -48,15 +48,16 @@ def _q_scale(head_dim: int) -> float:
 class ForwardContext:
     """Per-forward shared state: row positions, rotary tables (computed once, not per
     layer) and the LayerNorm-statistics plumbing of the fused path."""
-    __slots__ = ('pos', 'cos', 'sin', 'sums', 'part_a', 'part_b', 'fold', 'exact_attn', 'x32', 'order', 'scratch', 'f16', 'xs', 'plan', 'probe', 'ovf', 'cos32', 'sin32', 'guard', 'lora_x', 'contacts')
+    __slots__ = ('pos', 'cos', 'sin', 'sums', 'part_a', 'part_b', 'fold', 'exact_attn', 'x32', 'order', 'scratch', 'f16', 'xs', 'plan', 'probe', 'ovf', 'cos32', 'sin32', 'guard', 'lora_x', 'contacts',
+                 'sites', 'fast_site')
 
-    def __init__(self, pos, cos, sin, fold=False, exact_attn=False, f16=False, plan=None):
+    def __init__(self, pos, cos, sin, fold=False, exact_attn=False, f16=False, plan=None, cos32=None, sin32=None, probe=None, ovf=None, guard=None):
         self.pos, self.cos, self.sin = pos, cos, sin
         self.plan = plan            # precision 'half': HalfPlan (which robustness measures this model needs) or None
-        self.probe = None           # calibration forward: list collecting a per-layer upper bound of |attention score|
-        self.ovf = None             # precision 'half': int32 device flag of the run-time range guard (esme_gemm_fusion_t.overflow_flag)
-        self.guard = None           # precision 'half': HalfGuard -- the device maxima the plan is checked against (esme_gemm_fusion_t.col_absmax / .qk_sumsq)
-        self.cos32 = self.sin32 = None    # precision 'half': float32 rotary tables of the layers whose q / k travel as pairs
+        self.probe = probe          # calibration forward: list collecting a per-layer upper bound of |attention score|
+        self.ovf = ovf              # precision 'half': int32 device flag of the run-time range guard (esme_gemm_fusion_t.overflow_flag)
+        self.guard = guard          # precision 'half': HalfGuard -- the device maxima the plan is checked against (esme_gemm_fusion_t.col_absmax / .qk_sumsq)
+        self.cos32, self.sin32 = cos32, sin32    # precision 'half': float32 rotary tables of the layers whose q / k travel as pairs
         self.f16 = f16              # precision 'half': IEEE fp16 MFMA operands (weights converted once, activations rounded to fp16)
         self.fold = fold            # run the LN-folded fast path
         self.exact_attn = exact_attn    # high-precision mode: classic online softmax, every row maximum exact
@@ -69,6 +70,40 @@ class ForwardContext:
         self.part_b = None
         self.contacts = None        # predict_contacts: esme.contacts.ContactAccumulator -- every attention block hands it its final (q, k)
         self.lora_x = None          # LoRA: the (T, E + X) buffer whose first E columns ARE the residual stream; the last X hold the QKV adapters' down-projection
+        self.sites = None           # 'high' / 'half': per residual epilogue (layer i attention: 2 i, FFN: 2 i + 1) the keyword arguments that name the stream
+        self.fast_site = None       # 'fast': the same for the bf16 stream (one dict while the layers run in place)
+
+    def fp32_stream(self, x32, x16, n_layers):
+        """precision 'high': the residual epilogues add into the fp32 stream `x32` and write its bf16 rounding to `x16`."""
+        self.x32 = x32
+        self.sites = [{'resid32': x32, 'out': x16}] * (2 * n_layers)
+
+    def pair_stream(self, xs, scales):
+        """precision 'half': the residual epilogues update the float16 pair `xs` = [hi | ext | lo] in place.  `scales`: per layer
+        ((rho, 1 / rho) of the attention LayerNorm, the same of the FFN LayerNorm) (stream_scale()).  The pair travels SCALED per column by rho
+        of the LayerNorm whose folded GEMM reads it next (_fold_layernorm_pow2): it arrives scaled for a layer's attention LayerNorm, the
+        out-projection hands it on scaled for the FFN LayerNorm, the down-projection for the next layer's attention LayerNorm (None after the
+        last layer: the final LayerNorm reads x itself).  With massive channels (plan.ext_sel) the epilogues also refresh the extension tile;
+        with a guard they keep the column maxima of the stream after each branch (HalfGuard.col rows 1 + 2 i, 2 + 2 i)."""
+        self.xs = xs
+        ext = self.plan.ext_sel if self.plan is not None else None
+        col = self.guard.col if self.guard is not None else None
+        self.sites = sites = []
+        for i, ((_, a_inv), (f_rho, f_inv)) in enumerate(scales):
+            nxt = scales[i + 1][0][0] if i + 1 < len(scales) else None
+            for scale in ((a_inv, f_rho), (f_inv, nxt)):
+                sites.append({'resid_pair': xs, 'pair_scale': scale, 'pair_ext': ext, 'col_absmax': col[len(sites) + 1] if col is not None else None})
+
+    def residual(self, layer, branch, resid=None, out=None):
+        """Keyword arguments of _hip.gemm_fused(..., EPI_RESIDUAL) that name the residual stream at layer `layer`, branch 0 (attention) or 1
+        (FFN): the fp32 stream ('high'), the float16 pair with its scalings, extension tile and guard row ('half'), or the bf16 tensors
+        `resid` -> `out` ('fast')."""
+        if self.sites is not None:
+            return self.sites[2 * layer + branch]
+        site = self.fast_site
+        if site is None or site['resid'] is not resid or site['out'] is not out:
+            site = self.fast_site = {'resid': resid, 'out': out}
+        return site
 
 
 SUPPORTED_HEAD_DIMS = (16, 32, 64, 128)        # head dims of the attention / fused-rotary kernels
@@ -446,13 +481,13 @@ class FlashMultiheadAttention(nn.Module):
                                 softmax_scale=self.head_dim ** -0.5, exact=exact, order=order, q_prescaled=q_prescaled, out=out)
 
     def forward(self, x, cu_lens, max_len, lora_names=None, ctx: Optional[ForwardContext] = None,
-                resid=None, alpha: float = 1.0, out=None, x_stats=None, stats_out=None, resid32=None, resid_pair=None, pair_scale=None,
-                pair_ext=None):
+                resid=None, alpha: float = 1.0, out=None, x_stats=None, stats_out=None, stream=None):
         """Attention branch.  With `resid` given the out-projection epilogue returns
         resid + alpha * (attn @ W_o^T + b_o) (written to `out`, which may alias resid).
         `x_stats` ((nblk, T, 2) f32 partial row sums of x) selects the LN-folded projection;
-        `stats_out` makes the out-projection emit the statistics of its output.  `resid32` (high-precision mode): the fp32
-        residual stream, updated in place by the out-projection's epilogue; `out` receives its bf16 rounding.
+        `stats_out` makes the out-projection emit the statistics of its output.  `stream` (the model's forward; instead of `resid` / `out`):
+        ForwardContext.residual(...) of this site -- in the modes 'high' / 'half' the fp32 / float16-pair residual stream that the
+        out-projection's epilogue updates in place.
         `lora_names`: on a block with LoRA adapters (ESM2.add_lora), the adapters to apply (None / empty: all of them)."""
         T = x.shape[0]
         E = self.attn_dim                                   # width of each of q, k, v (H * padded head dim)
@@ -460,7 +495,7 @@ class FlashMultiheadAttention(nn.Module):
         if self._has_lora:
             if self.training:
                 raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
-            if resid32 is not None or resid_pair is not None or (ctx is not None and (ctx.f16 or ctx.exact_attn)):
+            if ctx is not None and (ctx.f16 or ctx.exact_attn):
                 raise NotImplementedError("LoRA adapters run in precision 'fast' only ('high', 'half' and 'exact' have no adapter path)")
             lw = self._lora_weights(lora_names, x_stats is not None)
         H, d = self.num_heads, self.head_pad
@@ -470,14 +505,16 @@ class FlashMultiheadAttention(nn.Module):
         qk_pass = (self.pre_layernorm and self.rot_emb is not None and ctx is not None and d in (16, 32, 64, 128) and E <= 5120)
         f16 = bool(ctx is not None and ctx.f16)
         qp = bool(_ATTN_QP and (rot_fusable or qk_pass) and d in (32, 64) and E % 64 == 0 and x_stats is not None and not ctx.exact_attn and not f16)
-        if f16 and (x_stats is None or (resid32 is None and resid_pair is None) or (self.pre_layernorm and not qk_pass)):
+        if f16 and (x_stats is None or ctx.sites is None or (self.pre_layernorm and not qk_pass)):
             raise NotImplementedError("precision='half' runs the LayerNorm-folded path on the fp32 / pair stream (ESM-C: with the fused q/k pass)")
         plan = ctx.plan if (f16 and ctx is not None) else None
         qk_pair = bool(plan is not None and plan.pairs_at(self.layer_index))
         if f16 and plan is not None and plan.qp and not qk_pair:      # precision 'half', fixed-reference attention (esme_hip_forward_half takes the same decision from attn_q_prescale)
             qp = bool((rot_fusable or qk_pass) and d in (32, 64) and E % 64 == 0 and not ctx.exact_attn)
         guard = ctx.guard if (f16 and ctx is not None) else None
-        g_col = guard.col[2 * self.layer_index + 1] if guard is not None else None          # plan guard: column maxima of the stream after this branch
+        pair_ext = plan.ext_sel if plan is not None else None      # massive channels: x is then [hi | ext] (K = E + 64), the pair (T, 2E + 64)
+        if stream is None and resid is not None:
+            stream = {'resid': resid, 'out': out}
         if qk_pair:
             # precision 'half' on a model with large attention scores: q / k leave the LN-folded projection as fp16 (hi, lo) pairs, are rotated
             # with FP32 tables (ctx.cos / ctx.sin are float32 then) and multiplied in three MFMA passes; v, P and the output stay single fp16
@@ -490,8 +527,7 @@ class FlashMultiheadAttention(nn.Module):
                 ctx.probe.append(_score_bound(qkv[:, :E], qkv[:, E:2 * E], H, d, self.head_dim ** -0.5))
             a = _hip.attn_varlen_qkpair(qkv, cu_lens, max_len, H, d, self.head_dim ** -0.5, order=ctx.order)
             wo, bo = self._weights_out(True)
-            return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out, resid_pair=resid_pair,
-                                   pair_scale=pair_scale, pair_ext=pair_ext, col_absmax=g_col)
+            return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, alpha=alpha, stats_out=stats_out, **stream)
         if x_stats is not None:
             a_op, wf, c1, c2 = self._qkv_operands(x, x_stats, ctx, lw, f16, pair_ext)
             qkv = _hip.gemm_fused(a_op, wf, None, ln=(x_stats, self.embed_dim, self.norm.eps, c1, c2, ctx.ovf if ctx is not None else None), rot=rot,
@@ -521,9 +557,8 @@ class FlashMultiheadAttention(nn.Module):
             ctx.contacts.layer(self.layer_index, q, k, qp)
         a, wo, bo = self._out_operands(lw, f16, q, k, v, cu_lens, max_len, exact=bool(ctx is not None and ctx.exact_attn),
                                        order=ctx.order if ctx is not None else None, q_prescaled=qp)
-        if resid is not None or resid32 is not None or resid_pair is not None:
-            return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out, resid32=resid32, resid_pair=resid_pair,
-                                   pair_scale=pair_scale, pair_ext=pair_ext, col_absmax=g_col if resid_pair is not None else None)
+        if stream is not None:
+            return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, alpha=alpha, stats_out=stats_out, **stream)
         return _hip.gemm(a, wo, bo, out=out)
 
     # -- LoRA adapters (esme/lora.py): the delta rides in an extension K-tile of the projection's own GEMM --------------------
@@ -751,20 +786,20 @@ class FlashTransformerLayer(nn.Module):
                 _pad_rows(down.weight.data, self.phys_dim), _pad_last(down.bias.data, self.phys_dim) if down.bias is not None else None))
         return down.weight, down.bias
 
-    def _ffn(self, x, resid, alpha, out, x_stats=None, stats_out=None, resid32=None, resid_pair=None, pair_scale=None, pair_ext=None, ovf=None, col_absmax=None):
+    def _ffn(self, x, alpha, stream, x_stats=None, stats_out=None, ovf=None):
+        """FFN branch onto the residual stream `stream` (ForwardContext.residual(...), or {'resid': ..., 'out': ...})."""
         epi = _hip.EPI_GELU if self.final_activation == 'gelu' else _hip.EPI_SWIGLU
         f16 = x.dtype == torch.float16                       # precision 'half': the operand type travels with the tensors
         if x_stats is not None:
-            wf, _, c1, c2 = self._weights_up(True, f16, pair_ext)
+            wf, _, c1, c2 = self._weights_up(True, f16, stream.get('pair_ext'))
             u = _hip.gemm_fused(x, wf, None, epi, ln=(x_stats, self.embed_dim, self.final[0].eps, c1, c2, ovf))
         else:
             w, b, _, _ = self._weights_up(False)
             u = _hip.gemm_fused(self.final[0](x), w, b, epi)
         wd, bd = self._weights_down(f16)
-        return _hip.gemm_fused(u, wd, bd, _hip.EPI_RESIDUAL, resid, alpha, out, stats_out=stats_out, resid32=resid32, resid_pair=resid_pair,
-                               pair_scale=pair_scale, pair_ext=pair_ext, col_absmax=col_absmax if resid_pair is not None else None)
+        return _hip.gemm_fused(u, wd, bd, _hip.EPI_RESIDUAL, alpha=alpha, stats_out=stats_out, **stream)
 
-    def forward_high_precision(self, x16, cu_lens, max_len, ctx: ForwardContext, next_scale=None):
+    def forward_high_precision(self, x16, cu_lens, max_len, ctx: ForwardContext):
         """One layer with the residual stream in fp32 (`ctx.x32`, updated in place).  `x16` = bf16(stream) is the MFMA
         operand of the LayerNorm-folded GEMMs.  The two residual GEMMs add their fp32 accumulators straight into the stream
         (`esme_gemm_fusion_t.resid32`: the branch output is never rounded to bf16 on the way), write the stream's bf16
@@ -776,20 +811,10 @@ class FlashTransformerLayer(nn.Module):
             ctx.part_a = torch.empty(_hip.stats_blocks(T, E), T, 2, dtype=torch.float32, device=x16.device)
             ctx.part_b = torch.empty_like(ctx.part_a)
         # precision 'half': the stream is the float16 pair ctx.xs = [hi | lo] and x16 is its hi half (a view): the residual epilogues
-        # read and write the pair in place -- no fp32 tensor, no separate operand copy
-        # The pair travels SCALED per column by rho of the LayerNorm whose folded GEMM reads it next (_fold_layernorm_pow2): it arrives
-        # scaled for this layer's attention LayerNorm, the out-projection hands it on scaled for the FFN LayerNorm, the down-projection
-        # for the next layer's attention LayerNorm (`next_scale` = its rho; None after the last layer: the final LayerNorm reads x itself).
-        r32, rp = (None, ctx.xs) if ctx.f16 else (ctx.x32, None)
-        sa = sf = ext = None
-        if ctx.f16:
-            (_, a_inv), (f_rho, f_inv) = self.self_attn.stream_scale(), self.stream_scale()
-            sa, sf = (a_inv, f_rho), (f_inv, next_scale)
-            ext = ctx.plan.ext_sel if ctx.plan is not None else None      # massive channels: x16 is then [hi | ext] (K = E + 64), the pair (T, 2E + 64)
-        self.self_attn(x16, cu_lens, max_len, None, ctx, alpha=alpha, out=x16, x_stats=ctx.sums, stats_out=ctx.part_b,
-                       resid32=r32, resid_pair=rp, pair_scale=sa, pair_ext=ext)
-        self._ffn(x16, None, alpha, x16, x_stats=ctx.part_b, stats_out=ctx.part_a, resid32=r32, resid_pair=rp, pair_scale=sf, pair_ext=ext,
-                  ovf=ctx.ovf, col_absmax=ctx.guard.col[2 * self.self_attn.layer_index + 2] if (ctx.f16 and ctx.guard is not None) else None)
+        # read and write the pair in place -- no fp32 tensor, no separate operand copy (ForwardContext.pair_stream)
+        i = self.self_attn.layer_index
+        self.self_attn(x16, cu_lens, max_len, None, ctx, alpha=alpha, x_stats=ctx.sums, stats_out=ctx.part_b, stream=ctx.residual(i, 0))
+        self._ffn(x16, alpha, ctx.residual(i, 1), x_stats=ctx.part_b, stats_out=ctx.part_a, ovf=ctx.ovf)
         ctx.sums = ctx.part_a
 
     def forward_exact(self, cu_lens, max_len, ctx: ForwardContext):
@@ -859,12 +884,13 @@ class FlashTransformerLayer(nn.Module):
                 ctx.sums = _hip.row_sums(x)
                 ctx.part_a = torch.empty(_hip.stats_blocks(T, E), T, 2, dtype=torch.float32, device=x.device)
                 ctx.part_b = torch.empty_like(ctx.part_a)
-            self.self_attn(x, cu_lens, max_len, lora_names, ctx, resid=x, alpha=alpha, out=y,
-                           x_stats=ctx.sums, stats_out=ctx.part_b)
-            self._ffn(y, y, alpha, y, x_stats=ctx.part_b, stats_out=ctx.part_a)
+            i = self.self_attn.layer_index
+            site = ctx.residual(i, 0, x, y)
+            self.self_attn(x, cu_lens, max_len, lora_names, ctx, alpha=alpha, x_stats=ctx.sums, stats_out=ctx.part_b, stream=site)
+            self._ffn(y, alpha, site if inplace else ctx.residual(i, 1, y, y), x_stats=ctx.part_b, stats_out=ctx.part_a)
             ctx.sums = ctx.part_a                               # row sums of the layer output
             return y
         if self.padded:
             raise NotImplementedError('padded layouts need a folding context (ForwardContext(fold=True))')
         self.self_attn(x, cu_lens, max_len, lora_names, ctx, resid=x, alpha=alpha, out=y)
-        return self._ffn(y, y, alpha, y)
+        return self._ffn(y, alpha, {'resid': y, 'out': y})

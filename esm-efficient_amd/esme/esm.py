@@ -263,11 +263,8 @@ class ESM2(nn.Module):
             if plan is not None and plan.qk_pair:                 # q / k pairs are rotated with fp32 tables (in the projection's pair epilogue),
                 cos32, sin32 = rot.tables(int(max_len), device, torch.float32)      # the other layers with the mode's fp16 tables
             cos, sin = rot.tables(int(max_len), device, dt)
-        ctx = ForwardContext(pos, cos, sin, fold=self.fold_layernorm, exact_attn=self.precision == 'high',
-                             f16=self.precision == 'half', plan=plan)
-        ctx.cos32, ctx.sin32 = cos32, sin32
-        ctx.probe, ctx.ovf, ctx.guard = st.probe, ovf, guard
-        return ctx
+        return ForwardContext(pos, cos, sin, fold=self.fold_layernorm, exact_attn=self.precision == 'high', f16=self.precision == 'half',
+                              plan=plan, cos32=cos32, sin32=sin32, probe=st.probe, ovf=ovf, guard=guard)
 
     def check_overflow(self):
         """Raise OverflowError if a forward in precision 'half' since the last call saw a value leave IEEE fp16's range (|x| >= 65 504 in the
@@ -341,101 +338,113 @@ class ESM2(nn.Module):
         ctx = self._context(cu_lens, max_len, x.shape[0], x.device)
         if contacts is not None:
             ctx.contacts = contacts(cu_lens, max_len)
-        taps = []
-        E = self.embed_dim
-
-        T, Ep, dev = *x.shape, x.device
-
-        def final_buffers(pair=None):              # 'exact' / 'half': the final LayerNorm's (hi, lo) bf16 pair (or the one given) and its fp32 output
-            alloc = torch.zeros if self.padded else torch.empty
-            return pair if pair is not None else alloc(T, 2 * Ep, dtype=torch.bfloat16, device=dev), alloc(T, Ep, dtype=torch.float32, device=dev)
-
-        def one_c_call(entry, x32, *half_args):    # 'exact' / 'half': all layers + the final LayerNorm through `entry` of esme.cforward
-            pair, rep32 = final_buffers()
-            entry(self, x32, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin, pair, rep32, *half_args)
-            return self._finish_representation(pair if want_pair else rep32, [], pad_output, pad_args, pad_indices, cu_lens, pad_width)
-        if self.precision == 'exact':
-            # split-operand mode: fp32 residual stream, activation pairs, fp32 results (esme.attention.FlashTransformerLayer.forward_exact).
-            # Padded layouts (ESM2-35M): everything at the physical width, pad columns zero as in the other modes.
-            ctx.x32 = self._embedding_exact(x, tokens, pad_args, pad_indices)
-            if self.c_forward and not layers and _hip.TRACE is None and self._c_forward_ok('exact'):
-                # all layers + the final LayerNorm through ONE C call (esme_hip_forward_exact: the launches below, bit-identical)
-                from esme.cforward import forward_layers_exact
-                return one_c_call(forward_layers_exact, ctx.x32)
-            ctx.order = _hip.seq_order(cu_lens)
-            for i, layer in enumerate(self.layers):
-                layer.forward_exact(cu_lens, max_len, ctx)
-                if i in layers:
-                    taps.append(ctx.x32.clone())
-            ln = self.emb_layer_norm_after
-            pair, x = final_buffers(ctx.scratch.get('h'))
-            _hip.layernorm_split(ctx.x32, ln.weight, ln.bias, ln.eps, E, out=pair, out32=x, out_off=Ep)
-            if want_pair:
-                x, taps = pair, []
-        elif self.precision == 'half':
-            # fp16 MFMA operands: x16 = fp16(stream) is what the LayerNorm-folded GEMMs read; the final LayerNorm and the LM head run in
-            # the split-operand form (fp32 representation / logits)
-            x32 = self._embedding_exact(x, tokens, pad_args, pad_indices)
-            if self.c_forward and not layers and _hip.TRACE is None and self._c_forward_ok('half'):
-                # all layers + the final LayerNorm through ONE C call (esme_hip_forward_half: the launches below, bit-identical)
-                from esme.cforward import forward_layers_half
-                return one_c_call(forward_layers_half, x32, ctx.plan, ctx.ovf, ctx.cos32, ctx.sin32, ctx.guard)
-            # the stream as a float16 PAIR [hi | lo] (x = hi + lo: 22 significant bits): hi is the operand of the LayerNorm-folded GEMMs,
-            # the residual GEMMs read and write the pair in place (8 B per element in whole lines; an fp32 stream + operand copy is 10).
-            # Padded layouts (ESM2-35M): everything at the physical width, pad columns zero as in the fast mode.
-            # With massive channels (ctx.plan.ext_sel) the row is [hi | ext (64) | lo]: the LayerNorm-folded GEMMs read [hi | ext] (K = Ep + 64).
-            ext = ctx.plan.ext
-            ctx.xs = torch.empty(T, 2 * Ep + ext, dtype=torch.float16, device=x.device)
-            ctx.sums = torch.empty(1, T, 2, dtype=torch.float32, device=x.device)
-            # (stored scaled per column by rho of the first attention LayerNorm: attention._fold_layernorm_pow2)
-            scales = [layer.self_attn.stream_scale() for layer in self.layers]
-            _hip.stream_operand(x32, ctx.xs, ctx.sums, pair=True, scale=scales[0][0], ext_sel=ctx.plan.ext_sel,
-                                col_absmax=ctx.guard.col[0] if ctx.guard is not None else None)
-            del x32
-            x16 = ctx.xs[:, :Ep + ext]
-            ctx.order = _hip.seq_order(cu_lens)
-            last = len(self.layers) - 1
-            for i, layer in enumerate(self.layers):
-                layer.forward_high_precision(x16, cu_lens, max_len, ctx, next_scale=scales[i + 1][0] if i < last else None)
-                if i in layers:
-                    tap = _hip.pair_to_f32(ctx.xs, Ep)
-                    taps.append(tap * scales[i + 1][1] if i < last else tap)          # the raw layer output: undo the stream's column scaling
-            ln = self.emb_layer_norm_after
-            pair, x = final_buffers()
-            _hip.layernorm_split(ctx.xs, ln.weight, ln.bias, ln.eps, E, out=pair, out32=x, in_off=Ep + ext, out_off=Ep, overflow_flag=ctx.ovf)
-            if want_pair:
-                x, taps = pair, []
-        elif self.precision == 'high' and len(self.layers):
-            # fp32 residual stream; x (bf16) is kept as the rounded copy the GEMMs read
-            assert x.shape[1] % 64 == 0, 'high-precision mode needs a 64-aligned physical width'
-            ctx.x32 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-            ctx.sums = torch.empty(1, x.shape[0], 2, dtype=torch.float32, device=x.device)
-            _hip.residual_f32_(ctx.x32, x, 1.0, x, ctx.sums, init=True)
-            for i, layer in enumerate(self.layers):
-                layer.forward_high_precision(x, cu_lens, max_len, ctx)
-                if i in layers:
-                    taps.append(x.clone())
-            ln = self.emb_layer_norm_after
-            _hip.layernorm_f32(ctx.x32[:, :E], ln.weight, ln.bias, ln.eps, out=x[:, :E])
-        elif self.c_forward and not layers and ctx.contacts is None and _hip.TRACE is None and self._c_forward_ok():
-            from esme import cforward
-            cforward.forward_layers(self, x, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin)
-        else:
-            ctx.order = _hip.seq_order(cu_lens)     # longest sequences' attention work first (speed only; the C entry does the same)
-            if lora is not None:
-                x = self._lora_stream(x, lora, ctx)
-            for i, layer in enumerate(self.layers):
-                x = layer(x, cu_lens, max_len, lora, ctx, inplace=True)
-                if i in layers:
-                    taps.append(x.clone(memory_format=torch.contiguous_format) if lora is not None else x.clone())
-            if ctx.lora_x is not None:                                # the stream lives inside the wide buffer: the final LayerNorm moves it out
-                y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-                self.emb_layer_norm_after(x, out=y)
-                x = y
-            else:
-                self.emb_layer_norm_after(x[:, :E], out=x[:, :E])        # pad columns (if any) stay zero
-
+        # one mode, one method: (final-LayerNorm output, raw outputs of the layers in `layers`).  'high' without layers is the fast path.
+        mode = self.precision if self.precision in ('half', 'exact') or (self.precision == 'high' and len(self.layers)) else 'fast'
+        x, taps = getattr(self, '_run_' + mode)(x, (tokens, pad_args, pad_indices), cu_lens, max_len, ctx, layers, want_pair, lora)
         return self._finish_representation(x, taps, pad_output, pad_args, pad_indices, cu_lens, pad_width)
+
+    def _one_call(self, ctx, layers, mode) -> bool:
+        """May this forward take the one-call C entry of `mode` (esme.cforward)?  Not with `layers=[...]` taps, a contact accumulator or an
+        active launch trace: those need the per-layer module loop."""
+        return bool(self.c_forward and not layers and ctx.contacts is None and _hip.TRACE is None and self._c_forward_ok(mode))
+
+    def _final_pair(self, T, device, pair=None):
+        """'exact' / 'half': the final LayerNorm's (hi, lo) bf16 pair (or the one given) and its fp32 output."""
+        alloc = torch.zeros if self.padded else torch.empty
+        Ep = self.phys_dim
+        return pair if pair is not None else alloc(T, 2 * Ep, dtype=torch.bfloat16, device=device), alloc(T, Ep, dtype=torch.float32, device=device)
+
+    def _run_fast(self, x, embed_args, cu_lens, max_len, ctx, layers, want_pair, lora):
+        if self._one_call(ctx, layers, 'fast'):
+            from esme import cforward
+            return cforward.forward_layers(self, x, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin), []
+        taps, E = [], self.embed_dim
+        ctx.order = _hip.seq_order(cu_lens)     # longest sequences' attention work first (speed only; the C entry does the same)
+        if lora is not None:
+            x = self._lora_stream(x, lora, ctx)
+        for i, layer in enumerate(self.layers):
+            x = layer(x, cu_lens, max_len, lora, ctx, inplace=True)
+            if i in layers:
+                taps.append(x.clone(memory_format=torch.contiguous_format) if lora is not None else x.clone())
+        if ctx.lora_x is not None:                                # the stream lives inside the wide buffer: the final LayerNorm moves it out
+            y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+            self.emb_layer_norm_after(x, out=y)
+            return y, taps
+        self.emb_layer_norm_after(x[:, :E], out=x[:, :E])        # pad columns (if any) stay zero
+        return x, taps
+
+    def _run_high(self, x, embed_args, cu_lens, max_len, ctx, layers, want_pair, lora):
+        """fp32 residual stream; x (bf16) is kept as the rounded copy the GEMMs read."""
+        assert x.shape[1] % 64 == 0, 'high-precision mode needs a 64-aligned physical width'
+        taps, E = [], self.embed_dim
+        ctx.fp32_stream(torch.empty(x.shape, dtype=torch.float32, device=x.device), x, len(self.layers))
+        ctx.sums = torch.empty(1, x.shape[0], 2, dtype=torch.float32, device=x.device)
+        _hip.residual_f32_(ctx.x32, x, 1.0, x, ctx.sums, init=True)
+        for i, layer in enumerate(self.layers):
+            layer.forward_high_precision(x, cu_lens, max_len, ctx)
+            if i in layers:
+                taps.append(x.clone())
+        ln = self.emb_layer_norm_after
+        _hip.layernorm_f32(ctx.x32[:, :E], ln.weight, ln.bias, ln.eps, out=x[:, :E])
+        return x, taps
+
+    def _run_half(self, x, embed_args, cu_lens, max_len, ctx, layers, want_pair, lora):
+        """fp16 MFMA operands: hi of the pair stream is what the LayerNorm-folded GEMMs read; the final LayerNorm and the LM head run in
+        the split-operand form (fp32 representation / logits)."""
+        (T, Ep), dev = x.shape, x.device
+        x32 = self._embedding_exact(x, *embed_args)
+        if self._one_call(ctx, layers, 'half'):
+            # all layers + the final LayerNorm through ONE C call (esme_hip_forward_half: the launches below, bit-identical)
+            from esme.cforward import forward_layers_half
+            pair, rep32 = self._final_pair(T, dev)
+            forward_layers_half(self, x32, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin, pair, rep32, ctx.plan, ctx.ovf, ctx.cos32, ctx.sin32, ctx.guard)
+            return (pair if want_pair else rep32), []
+        # the stream as a float16 PAIR [hi | lo] (x = hi + lo: 22 significant bits): hi is the operand of the LayerNorm-folded GEMMs,
+        # the residual GEMMs read and write the pair in place (8 B per element in whole lines; an fp32 stream + operand copy is 10).
+        # Padded layouts (ESM2-35M): everything at the physical width, pad columns zero as in the fast mode.
+        # With massive channels (ctx.plan.ext_sel) the row is [hi | ext (64) | lo]: the LayerNorm-folded GEMMs read [hi | ext] (K = Ep + 64).
+        taps, ext = [], ctx.plan.ext
+        # (stored scaled per column by rho of the LayerNorm that reads it next: attention._fold_layernorm_pow2)
+        scales = [(layer.self_attn.stream_scale(), layer.stream_scale()) for layer in self.layers]
+        ctx.pair_stream(torch.empty(T, 2 * Ep + ext, dtype=torch.float16, device=dev), scales)
+        ctx.sums = torch.empty(1, T, 2, dtype=torch.float32, device=dev)
+        _hip.stream_operand(x32, ctx.xs, ctx.sums, pair=True, scale=scales[0][0][0], ext_sel=ctx.plan.ext_sel,
+                            col_absmax=ctx.guard.col[0] if ctx.guard is not None else None)
+        del x32
+        x16 = ctx.xs[:, :Ep + ext]
+        ctx.order = _hip.seq_order(cu_lens)
+        last = len(self.layers) - 1
+        for i, layer in enumerate(self.layers):
+            layer.forward_high_precision(x16, cu_lens, max_len, ctx)
+            if i in layers:
+                tap = _hip.pair_to_f32(ctx.xs, Ep)
+                taps.append(tap * scales[i + 1][0][1] if i < last else tap)          # the raw layer output: undo the stream's column scaling
+        ln = self.emb_layer_norm_after
+        pair, rep32 = self._final_pair(T, dev)
+        _hip.layernorm_split(ctx.xs, ln.weight, ln.bias, ln.eps, self.embed_dim, out=pair, out32=rep32, in_off=Ep + ext, out_off=Ep, overflow_flag=ctx.ovf)
+        return (pair, []) if want_pair else (rep32, taps)
+
+    def _run_exact(self, x, embed_args, cu_lens, max_len, ctx, layers, want_pair, lora):
+        """split-operand mode: fp32 residual stream, activation pairs, fp32 results (esme.attention.FlashTransformerLayer.forward_exact).
+        Padded layouts (ESM2-35M): everything at the physical width, pad columns zero as in the other modes."""
+        (T, Ep), dev = x.shape, x.device
+        ctx.x32 = self._embedding_exact(x, *embed_args)
+        if self._one_call(ctx, layers, 'exact'):
+            # all layers + the final LayerNorm through ONE C call (esme_hip_forward_exact: the launches below, bit-identical)
+            from esme.cforward import forward_layers_exact
+            pair, rep32 = self._final_pair(T, dev)
+            forward_layers_exact(self, ctx.x32, cu_lens, max_len, ctx.pos, ctx.cos, ctx.sin, pair, rep32)
+            return (pair if want_pair else rep32), []
+        taps = []
+        ctx.order = _hip.seq_order(cu_lens)
+        for i, layer in enumerate(self.layers):
+            layer.forward_exact(cu_lens, max_len, ctx)
+            if i in layers:
+                taps.append(ctx.x32.clone())
+        ln = self.emb_layer_norm_after
+        pair, rep32 = self._final_pair(T, dev, ctx.scratch.get('h'))
+        _hip.layernorm_split(ctx.x32, ln.weight, ln.bias, ln.eps, self.embed_dim, out=pair, out32=rep32, out_off=Ep)
+        return (pair, []) if want_pair else (rep32, taps)
 
     def _finish_representation(self, x, taps, pad_output, pad_args, pad_indices, cu_lens, pad_width):
         if pad_output or (pad_args is None):
