@@ -1508,7 +1508,10 @@ __global__ __launch_bounds__(256, 2) void attn_sb_kernel(const AttnSplitArgs sa)
 
 using namespace esme;
 
-template <int NW, bool QP = false, int D = 64, bool F16 = false>
+// ---- Kernel selection (pinned on the CPU by tests/test_kernel_launch_log_cpu.py): one launcher per kernel template; the entries choose
+// the instantiation through dispatch_head_dim / dispatch_flags (launch.h).
+
+template <int NW, bool QP, int D, bool F16>
 static int launch_pp64(AttnArgs& a, int B, int max_len, hipStream_t s) {
     constexpr int smem = 4 * (KT * D * 2 + D * 128);
     auto kern = attn_pp64_kernel<NW, QP, D, F16>;
@@ -1522,7 +1525,7 @@ static int launch_pp64(AttnArgs& a, int B, int max_len, hipStream_t s) {
 }
 
 template <int D, bool F16, bool QKP, bool QP>
-static int launch_sb(AttnSplitArgs& sa, int B, int max_len, hipStream_t s) {
+static int launch_sb(AttnSplitArgs sa, int B, int max_len, hipStream_t s) {
     constexpr int smem = 3 * ((QKP ? 2 : 1) * KT * D * 2 + D * 128);
     auto kern = attn_sb_kernel<D, F16, QKP, QP>;
     static std::atomic<unsigned long long> done{0ull};         // dynamic-LDS attribute: per (kernel, device)
@@ -1553,6 +1556,41 @@ static int generic_launch_ok(int64_t ld_qkv, int max_len, int rows, int B, const
     return ESME_OK;
 }
 
+// `a` for sequences [b0, b0 + nb): cu_lens advanced to the first of them
+static AttnArgs sequence_chunk(AttnArgs a, int b0, int nb) {
+    a.cu += b0;
+    a.nhb = a.H * nb;
+    return a;
+}
+
+// the first-generation kernel: QB 32-row q-blocks per wave
+template <int D, int QB, bool F16>
+static int launch_generic(const AttnArgs& a, int B, int max_len, hipStream_t s) {
+    constexpr int rows = QT * QB;
+    if (const int rc = generic_launch_ok(a.ld, max_len, rows, B, a.order, "attn")) return rc;
+    return for_sequence_chunks(B, kMaxGridZ, [&](int b0, int nb) {
+        const dim3 grid((unsigned int)((max_len + rows - 1) / rows), (unsigned int)a.H, (unsigned int)nb);
+        hipLaunchKernelGGL((attn_varlen_kernel<D, QB, F16>), grid, dim3(256), 0, s, sequence_chunk(a, b0, nb));
+        return check_launch("attn_varlen_fwd");
+    });
+}
+
+template <int D, bool F16, bool QKP>
+static int launch_split(const AttnSplitArgs& sa, int B, int max_len, const char* what, hipStream_t s) {
+    constexpr int smem = 2 * (2 * KT * D * 2 + (QKP ? 1 : 2) * D * 128);
+    if (const int rc = generic_launch_ok(sa.a.ld, max_len, QT, B, sa.a.order, what)) return rc;
+    auto kern = attn_split_kernel<D, F16, QKP>;
+    if (smem >= 64 * 1024) {
+        static std::atomic<unsigned long long> done{0ull};
+        if (const int rc = raise_dynamic_lds(done, kern, smem, "attn_split")) return rc;
+    }
+    return for_sequence_chunks(B, kMaxGridZ, [&](int b0, int nb) {
+        const dim3 grid((unsigned int)((max_len + QT - 1) / QT), (unsigned int)sa.a.H, (unsigned int)nb);
+        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, AttnSplitArgs{sequence_chunk(sa.a, b0, nb), sa.lo_in, sa.lo_out});
+        return check_launch("attn_varlen_fwd_split");
+    });
+}
+
 // The checks that open all three attention entries, under the entry's message prefix `pre`: sizes, then the empty-batch return
 // (*empty set, ESME_OK), null pointers, the entry's own stride / pair-offset condition (`strides_ok`, named `strides_what` in the
 // message), alignment, max_len / H.  The caller returns at once when the result is non-zero or *empty is set.
@@ -1572,15 +1610,26 @@ static int attn_entry_checks(const char* pre, const void* q, const void* k, cons
     return ESME_OK;
 }
 
+// the argument block of every kernel: exact maxima (thr = 0, spec = 0) unless the caller sets them
+static AttnArgs attn_args(const void* q, const void* k, const void* v, int64_t ld_qkv, void* o, int64_t ld_o, const int32_t* cu_lens, int B, int H,
+                          float scale_log2, const int32_t* seq_order) {
+    return AttnArgs{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H, scale_log2, 1, H * B, 0.0f, 0, seq_order};
+}
+static constexpr float kLog2e = 1.4426950408889634f;
+
+// The pipelined kernels (attn_pp64_kernel, attn_sb_kernel) exist for head dims 64 and 32, store whole 16-byte chunks of o, and address K / V
+// with 32-bit byte offsets inside one sequence: (max_len + one tile) rows must fit.
+static bool pipelined_ok(int d, const void* o, int64_t ld_o, int64_t ld_qkv, int max_len) {
+    return (d == 64 || d == 32) && ld_o % 8 == 0 && aligned16(o) && ((int64_t)max_len + KT) * ld_qkv * 2 < 0xffffffffLL;
+}
+
 // (per-call options, esme_attn_opts_t: no process-global tuning state; NULL = the defaults below)
 static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv, void* o, int64_t ld_o, const int32_t* cu_lens,
                     int B, int64_t T, int H, int d, int max_len, float softmax_scale, void* stream, bool exact,
                     const esme_attn_opts_t* opts) {
     ESME_CHECK_ARG(!opts || opts->struct_bytes == (int)sizeof(esme_attn_opts_t), "attn: options struct of another ABI");
-    const int g_attn_variant = opts ? opts->variant : 0;       // 0 = heuristic, 1 = first-generation kernel, 4 / 8 = ping-pong with 4 / 8 waves
-    const int g_force_qb = opts ? opts->q_blocks : 0;          // first-generation kernel: q-blocks per wave (0 = heuristic)
-    const float g_attn_thr = opts ? opts->defer_max_thr : 8.0f;   // defer-max threshold, log2 units
-    const int g_attn_spec = opts ? opts->speculative : 1;      // speculative softmax in the ping-pong kernel
+    const int variant = opts ? opts->variant : 0;              // 0 = heuristic, 1 = first-generation kernel, 2 = single-block pipelined, 4 / 8 = ping-pong with 4 / 8 waves
+    const int force_qb = opts ? opts->q_blocks : 0;            // first-generation kernel: q-blocks per wave (0 = heuristic)
     bool empty;
     if (const int rc = attn_entry_checks("attn", q, k, v, o, cu_lens, B, T, H, d, max_len,
                                          ld_qkv % 8 == 0 && ld_qkv >= (int64_t)H * d && ld_o % 4 == 0 && ld_o >= (int64_t)H * d,
@@ -1592,85 +1641,33 @@ static int attn_fwd(const void* q, const void* k, const void* v, int64_t ld_qkv,
     ESME_CHECK_ARG(!(f16 && qp) || ((d == 64 || d == 32) && ld_o % 8 == 0 && aligned16(o)),
                    "attn: fp16 operands combine with q_prescaled for head dims 64 / 32 only (the ping-pong kernel's fixed-reference form; "
                    "variants 1 / 2, and strides for which (max_len + 64) rows pass 2^32 bytes, run the generic kernel with a unit scale)");
+    AttnArgs a = attn_args(q, k, v, ld_qkv, o, ld_o, cu_lens, B, H, qp ? 1.0f : softmax_scale * kLog2e, opts ? opts->seq_order : nullptr);
+    if (!exact) { a.thr = opts ? opts->defer_max_thr : 8.0f; a.spec = opts ? opts->speculative : 1; }      // defer-max threshold (log2 units); speculative softmax in the ping-pong kernel
+    const hipStream_t s = (hipStream_t)stream;
+    const char* const bad_dim = "attn: head dim must be 16, 32, 64 or 128";
     // f16 + q_prescaled with variant 1 or 2: neither the first-generation nor the single-block kernel has the prescaled fp16 form, so these
     // go to the generic kernel below with c = 1 (an exact-maximum online softmax in log2 units), as a stride that does not fit 32 bits does
-    const bool generic_qp16 = f16 && qp && (g_attn_variant == 1 || g_attn_variant == 2);
-    AttnArgs a{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H,
-               qp ? 1.0f : softmax_scale * 1.4426950408889634f, 1, H * B, exact ? 0.0f : g_attn_thr, exact ? 0 : g_attn_spec,
-               opts ? opts->seq_order : nullptr};
-    const hipStream_t s = (hipStream_t)stream;
-    // (the ping-pong kernel addresses K / V with 32-bit byte offsets inside one sequence: (max_len + one tile) rows must fit)
-    const bool fits32 = ((int64_t)max_len + KT) * ld_qkv * 2 < 0xffffffffLL;
-    if ((d == 64 || d == 32) && g_attn_variant == 2 && ld_o % 8 == 0 && aligned16(o) && fits32 && !generic_qp16) {
+    const bool pipelined = pipelined_ok(d, o, ld_o, ld_qkv, max_len) && !(f16 && qp && (variant == 1 || variant == 2));
+    if (pipelined && variant == 2)
         // per-call option 2: the single-block pipelined kernel (attn_sb_kernel: 128 query rows per workgroup) -- what the q/k-pair entry runs; here for
         // A/B measurements of the plain forms against the ping-pong kernel
-        AttnSplitArgs sa{a, 0, 0};
-        if (d == 64) return f16 ? launch_sb<64, true, false, false>(sa, B, max_len, s) : (qp ? launch_sb<64, false, false, true>(sa, B, max_len, s) : launch_sb<64, false, false, false>(sa, B, max_len, s));
-        return f16 ? launch_sb<32, true, false, false>(sa, B, max_len, s) : (qp ? launch_sb<32, false, false, true>(sa, B, max_len, s) : launch_sb<32, false, false, false>(sa, B, max_len, s));
-    }
-    if (d == 64 && g_attn_variant != 1 && ld_o % 8 == 0 && aligned16(o) && fits32 && !generic_qp16) {
-        // head dim 64 (ESM2-650M / 3B, ESM-C): the software-pipelined kernel.  4 waves = 256 query rows per workgroup, two
-        // workgroups per CU (one's prologue / epilogue overlaps the other's main loop): measured faster than 8 waves
-        // (one workgroup per CU) from S = 130 to S = 2 000; the 8-wave form stays behind the tuning hook.
-        const int nw = g_attn_variant == 8 ? 8 : 4;
-        if (f16) return qp ? launch_pp64<4, true, 64, true>(a, B, max_len, s) : launch_pp64<4, false, 64, true>(a, B, max_len, s);
-        if (qp && nw == 4) return launch_pp64<4, true>(a, B, max_len, s);
-        return nw == 8 ? launch_pp64<8>(a, B, max_len, s) : launch_pp64<4>(a, B, max_len, s);
-    }
-    if (d == 32 && g_attn_variant != 1 && ld_o % 8 == 0 && aligned16(o) && fits32 && !generic_qp16) {
-        // head dim 32 (ESM2-150M; ESM2-35M's padded heads): the same software-pipelined kernel at D = 32 (round 4)
-        if (f16) return qp ? launch_pp64<4, true, 32, true>(a, B, max_len, s) : launch_pp64<4, false, 32, true>(a, B, max_len, s);
-        return qp ? launch_pp64<4, true, 32>(a, B, max_len, s) : launch_pp64<4, false, 32>(a, B, max_len, s);
+        return dispatch_head_dim<64, 32>(d, bad_dim, [&](auto D) {
+            return dispatch_flags([&](auto F16, auto QP) { return launch_sb<D(), F16(), false, QP() && !F16()>(AttnSplitArgs{a, 0, 0}, B, max_len, s); }, f16, qp);
+        });
+    if (pipelined && variant != 1) {
+        // The software-pipelined kernel: head dim 64 (ESM2-650M / 3B, ESM-C) and, since round 4, 32 (ESM2-150M; ESM2-35M's padded heads).  4 waves = 256
+        // query rows per workgroup, two workgroups per CU (one's prologue / epilogue overlaps the other's main loop): measured faster than 8 waves (one
+        // workgroup per CU) from S = 130 to S = 2 000; the 8-wave form (bf16, head dim 64, reference maximum) stays behind the tuning hook.
+        if (variant == 8 && d == 64 && !f16) return launch_pp64<8, false, 64, false>(a, B, max_len, s);
+        return dispatch_head_dim<64, 32>(d, bad_dim, [&](auto D) {
+            return dispatch_flags([&](auto F16, auto QP) { return launch_pp64<4, QP(), D(), F16()>(a, B, max_len, s); }, f16, qp);
+        });
     }
     // two 32-row q-blocks per wave when the longest sequence fills at least one 256-row tile
     // (head dim 128 keeps one: its accumulators alone take 128 VGPRs per q-block)
-    const int qb = (g_force_qb ? g_force_qb : (max_len >= 192 ? 2 : 1));
-    const bool two = qb == 2 && d <= 64;
-    const int rows = QT * (two ? 2 : 1);
-    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn: head dim must be 16, 32, 64 or 128");
-    if (const int rc = generic_launch_ok(ld_qkv, max_len, rows, B, a.order, "attn")) return rc;
-    const hipStream_t s0 = s;
-    // sequence index on grid z (at most 65 535): chunks of sequences, each with cu_lens advanced to its first sequence
-    return for_sequence_chunks(B, kMaxGridZ, [&](int b0, int nb) {
-        AttnArgs ac = a;
-        ac.cu = cu_lens + b0;
-        ac.nhb = H * nb;
-        const dim3 grid((unsigned int)((max_len + rows - 1) / rows), (unsigned int)H, (unsigned int)nb), block(256);
-#define ESME_ATTN(DD)                                                                         \
-    case DD:                                                                                   \
-        if (f16) {                                                                             \
-            if (two) hipLaunchKernelGGL((attn_varlen_kernel<DD, (DD <= 64 ? 2 : 1), true>), grid, block, 0, s0, ac); \
-            else hipLaunchKernelGGL((attn_varlen_kernel<DD, 1, true>), grid, block, 0, s0, ac);  \
-        } else if (two) hipLaunchKernelGGL((attn_varlen_kernel<DD, (DD <= 64 ? 2 : 1)>), grid, block, 0, s0, ac); \
-        else hipLaunchKernelGGL((attn_varlen_kernel<DD, 1>), grid, block, 0, s0, ac);            \
-        break;
-        switch (d) {
-            ESME_ATTN(16)
-            ESME_ATTN(32)
-            ESME_ATTN(64)
-            ESME_ATTN(128)
-        }
-#undef ESME_ATTN
-        return check_launch("attn_varlen_fwd");
-    });
-}
-
-template <int D, bool F16 = false, bool QKP = false>
-static int launch_split(const AttnSplitArgs& sa, int B, int max_len, hipStream_t s) {
-    constexpr int smem = 2 * (2 * KT * D * 2 + (QKP ? 1 : 2) * D * 128);
-    auto kern = attn_split_kernel<D, F16, QKP>;
-    if (smem >= 64 * 1024) {
-        static std::atomic<unsigned long long> done{0ull};
-        if (const int rc = raise_dynamic_lds(done, kern, smem, "attn_split")) return rc;
-    }
-    // sequence index on grid z (at most 65 535): chunks of sequences, each with cu_lens advanced to its first sequence
-    return for_sequence_chunks(B, kMaxGridZ, [&](int b0, int nb) {
-        AttnSplitArgs sc = sa;
-        sc.a.cu = sa.a.cu + b0;
-        sc.a.nhb = sa.a.H * nb;
-        const dim3 grid((unsigned int)((max_len + QT - 1) / QT), (unsigned int)sa.a.H, (unsigned int)nb);
-        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, sc);
-        return check_launch("attn_varlen_fwd_split");
+    const bool two = (force_qb ? force_qb : (max_len >= 192 ? 2 : 1)) == 2;
+    return dispatch_head_dim<16, 32, 64, 128>(d, bad_dim, [&](auto D) {
+        return dispatch_flags([&](auto F16, auto TWO) { return launch_generic<D(), (TWO() && D() <= 64) ? 2 : 1, F16()>(a, B, max_len, s); }, f16, two);
     });
 }
 
@@ -1682,45 +1679,30 @@ extern "C" int esme_hip_attn_varlen_fwd_split(const void* q, const void* k, cons
                                          ld_qkv % 8 == 0 && lo_qkv % 8 == 0 && lo_qkv > 0 && ld_o % 4 == 0 && lo_o % 4 == 0 &&
                                              lo_o >= (int64_t)H * d && ld_o >= lo_o + (int64_t)H * d,
                                          "bad row strides / pair offsets", &empty); rc || empty) return rc;
-    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_split: head dim must be 16, 32, 64 or 128");
-    if (const int rc = generic_launch_ok(ld_qkv, max_len, QT, B, seq_order, "attn_split")) return rc;
-    AttnSplitArgs sa{{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H, softmax_scale * 1.4426950408889634f, 1, H * B,
-                      0.0f, 0, seq_order}, lo_qkv, lo_o};
-    const hipStream_t s = (hipStream_t)stream;
-    switch (d) {
-        case 16: return launch_split<16>(sa, B, max_len, s);
-        case 32: return launch_split<32>(sa, B, max_len, s);
-        case 64: return launch_split<64>(sa, B, max_len, s);
-        case 128: return launch_split<128>(sa, B, max_len, s);
-        default: ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_split: head dim must be 16, 32, 64 or 128");
-    }
+    const AttnSplitArgs sa{attn_args(q, k, v, ld_qkv, o, ld_o, cu_lens, B, H, softmax_scale * kLog2e, seq_order), lo_qkv, lo_o};
+    return dispatch_head_dim<16, 32, 64, 128>(d, "attn_split: head dim must be 16, 32, 64 or 128", [&](auto D) {
+        return launch_split<D(), false, false>(sa, B, max_len, "attn_split", (hipStream_t)stream);
+    });
 }
 
 extern "C" int esme_hip_attn_varlen_fwd_qkpair_f16_opts(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t lo_qk, void* o,
                                                         int64_t ld_o, const int32_t* cu_lens, int B, int64_t T, int H, int d,
                                                         int max_len, float softmax_scale, const esme_attn_opts_t* opts, void* stream) {
     ESME_CHECK_ARG(!opts || opts->struct_bytes == (int)sizeof(esme_attn_opts_t), "attn_qkpair: options struct of another ABI");
-    const int32_t* seq_order = opts ? opts->seq_order : nullptr;
     bool empty;
     if (const int rc = attn_entry_checks("attn_qkpair", q, k, v, o, cu_lens, B, T, H, d, max_len,
                                          ld_qkv % 8 == 0 && lo_qk % 8 == 0 && lo_qk > 0 && ld_o % 4 == 0 && ld_o >= (int64_t)H * d,
                                          "bad row strides / pair offset", &empty); rc || empty) return rc;
-    AttnSplitArgs sa{{(const u16*)q, (const u16*)k, (const u16*)v, ld_qkv, (u16*)o, ld_o, cu_lens, H, softmax_scale * 1.4426950408889634f, 1, H * B,
-                      0.0f, 0, seq_order}, lo_qk, 0};
+    const AttnSplitArgs sa{attn_args(q, k, v, ld_qkv, o, ld_o, cu_lens, B, H, softmax_scale * kLog2e, opts ? opts->seq_order : nullptr), lo_qk, 0};
     const hipStream_t s = (hipStream_t)stream;
     // options variant 2, head dims 64 / 32: the key-axis-pipelined kernel (round 6; exact maxima: spec = 0, thr = 0).  Measured (profiles/r06_attn_sb_bench.txt):
     // 404 vs 363 us at 100 x 500, 636 vs 641 at 49 x 1 002, 1 140 vs 1 168 at 25 x 2 000 -- not the hoped-for 260 us, so the first-generation kernel stays the default
-    const bool fits32 = ((int64_t)max_len + KT) * ld_qkv * 2 < 0xffffffffLL;
-    if ((d == 64 || d == 32) && opts && opts->variant == 2 && ld_o % 8 == 0 && aligned16(o) && fits32)
-        return d == 64 ? launch_sb<64, true, true, false>(sa, B, max_len, s) : launch_sb<32, true, true, false>(sa, B, max_len, s);
-    if (d != 16 && d != 32 && d != 64) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_qkpair: head dim must be 16, 32 or 64");
-    if (const int rc = generic_launch_ok(ld_qkv, max_len, QT, B, seq_order, "attn_qkpair")) return rc;
-    switch (d) {
-        case 16: return launch_split<16, true, true>(sa, B, max_len, s);
-        case 32: return launch_split<32, true, true>(sa, B, max_len, s);
-        case 64: return launch_split<64, true, true>(sa, B, max_len, s);
-        default: ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_qkpair: head dim must be 16, 32 or 64");
-    }
+    const char* const bad_dim = "attn_qkpair: head dim must be 16, 32 or 64";
+    if (opts && opts->variant == 2 && pipelined_ok(d, o, ld_o, ld_qkv, max_len))
+        return dispatch_head_dim<64, 32>(d, bad_dim, [&](auto D) { return launch_sb<D(), true, true, false>(sa, B, max_len, s); });
+    return dispatch_head_dim<16, 32, 64>(d, bad_dim, [&](auto D) {
+        return launch_split<D(), true, true>(sa, B, max_len, "attn_qkpair", s);
+    });
 }
 
 extern "C" int esme_hip_attn_varlen_fwd_qkpair_f16(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t lo_qk, void* o,

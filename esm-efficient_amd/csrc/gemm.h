@@ -7,31 +7,31 @@
 namespace esme {
 
 struct GemmArgs {
-    const u16* A; int64_t lda;
-    const u16* W;
-    const u16* bias;
-    const u16* resid; int64_t ldr;
-    u16* C; int64_t ldc;
-    int64_t M; int N; int K;
-    float alpha;
-    int tiles_n;
-    int vec_ok;                  // C rows allow 16-byte stores (ldc % 8 == 0, 16-B aligned) and resid rows 8-byte loads
+    const u16* A = nullptr; int64_t lda = 0;
+    const u16* W = nullptr;
+    const u16* bias = nullptr;
+    const u16* resid = nullptr; int64_t ldr = 0;
+    u16* C = nullptr; int64_t ldc = 0;
+    int64_t M = 0; int N = 0; int K = 0;
+    float alpha = 0.f;
+    int tiles_n = 0;
+    int vec_ok = 0;              // C rows allow 16-byte stores (ldc % 8 == 0, 16-B aligned) and resid rows 8-byte loads
     // fused rotary (QKV projection): columns < rot_cols are rotated with position pos[m]
-    const u16* cosT; const u16* sinT; const int32_t* pos; int max_len; int rot_cols;
+    const u16* cosT = nullptr; const u16* sinT = nullptr; const int32_t* pos = nullptr; int max_len = 0; int rot_cols = 0;
     // tile rasterisation: bands of gm tile-rows, inside a band groups of gn tile-columns walked
     // column-major (gm = 1, gn = tiles_n is plain row-major)
-    int tiles_m, gm, gn;
-    int nt_store;                // TRACE build only: 2 = skip the C stores, 3 = skip the whole epilogue (timing experiments)
-    int stagger;                 // TRACE build only: first-round start skew (units of ~1024 cycles across the 256 first blocks)
+    int tiles_m = 0, gm = 1, gn = 1;
+    int nt_store = 0;            // TRACE build only: 2 = skip the C stores, 3 = skip the whole epilogue (timing experiments)
+    int stagger = 0;             // TRACE build only: first-round start skew (units of ~1024 cycles across the 256 first blocks)
     // LayerNorm folded into the consumer GEMM (W already scaled by gamma):
     //   y = rstd[m]*acc - (rstd*mean)[m]*c1[n] + c2[n];  mean/rstd of row m are reduced in-kernel from
     //   ln_partial (ln_nblk, M, 2): per-block (sum, sum of squares) over ln_dim features
-    const float* ln_partial; int ln_nblk; int ln_dim; float ln_eps; const float* ln_c1; const float* ln_c2;
+    const float* ln_partial = nullptr; int ln_nblk = 0; int ln_dim = 0; float ln_eps = 0.f; const float* ln_c1 = nullptr; const float* ln_c2 = nullptr;
     // residual epilogue also emits per-row partial (sum, sum of squares) of the ROUNDED output
     // over each column tile of the launch: stats_out[(n/BN) * M + m] (float2) -> next LayerNorm's statistics
-    float* stats_out;
-    int64_t stat_ld = 0;         // row count of the FULL problem = block stride of ln_partial / stats_out ((nblk, stat_ld, 2));
-                                 // a launch may cover a row range of it (tail split, see esme_hip_gemm_bf16_fused)
+    float* stats_out = nullptr;
+    int64_t stat_ld = 0;         // the call's M = block stride of ln_partial / stats_out ((nblk, stat_ld, 2)); the second launch of a column
+                                 // split (esme_hip_gemm_bf16_opts) offsets stats_out by whole blocks of it
     unsigned long long* trace = nullptr;      // ESME_GEMM_TRACE builds only: per-block phase timestamps (16 per block)
     int opt_gm = 0, opt_gn = 0, opt_persist = -1;   // host side: per-call options (esme_gemm_opts_t); 0 / -1 = heuristic
     float q_scale = 0.f; int q_cols = 0;            // fused rotary: columns < q_cols leave multiplied by q_scale (softmax scale folded into q)

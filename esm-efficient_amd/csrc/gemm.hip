@@ -1137,15 +1137,82 @@ static int persist_default() {
     static const int v = [] { const char* e = getenv("ESME_GEMM_PERSIST"); return e ? (atoi(e) != 0) : 1; }();
     return v;
 }
-static int cu_count();
-#ifdef ESME_GEMM_TRACE
-static int g_nt_store = 0;                         // instrumented build only (libesme_hip_trace.so): timing experiments
-static int g_stagger = 0;
-#endif
+static int cu_count() {              // compute units of the current device (cached per device ordinal; 256 on MI355X)
+    static std::atomic<int> cached[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int v = cached[dev & 63].load(std::memory_order_relaxed);
+    if (v <= 0) {
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        cached[dev & 63].store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
 
-// Choose the tile walk.  If the whole weight matrix fits an XCD's L2 (4 MB) next to the
-// streaming activations, plain row-major order is already optimal (W stays resident, every
-// activation slab is fetched once).  Otherwise walk 8 x 4 groups (1 workgroup/CU, 32 CUs per
+// ---- Kernel selection (pinned on the CPU by tests/test_kernel_launch_log_cpu.py).  A validated call becomes a GemmForm: the kernel's
+// template parameters but the tile, which launch_gemm adds, and PERSIST, which launch_one adds.
+struct GemmForm {
+    int epi, rotd;
+    bool lnf, stats, r32, pair, f16, rp;
+    constexpr unsigned key() const { return epi | rotd << 2 | lnf << 9 | stats << 10 | r32 << 11 | pair << 12 | f16 << 13 | rp << 14; }
+};
+
+// The 38 shipped forms, X(EPI, ROTD, LNF, STATS, R32, PAIR, F16, RP); each is built for the 128 x 128 and the 256 x 256 tile.
+#define ESME_GEMM_FORMS(X)                                                                                                                                      \
+    /* split-operand mode, (hi, lo) bf16 pair output: plain with fused rotary, GELU, SwiGLU */                                                                  \
+    X(ESME_EPI_NONE, 0, 0, 0, 0, 1, 0, 0) X(ESME_EPI_NONE, 16, 0, 0, 0, 1, 0, 0) X(ESME_EPI_NONE, 32, 0, 0, 0, 1, 0, 0) X(ESME_EPI_NONE, 64, 0, 0, 0, 1, 0, 0)  \
+    X(ESME_EPI_GELU, 0, 0, 0, 0, 1, 0, 0) X(ESME_EPI_SWIGLU, 0, 0, 0, 0, 1, 0, 0)                                                                               \
+    /* precision 'half', q / k as pairs: the LN-folded projection writes (hi, lo), rotated with fp32 tables */                                                  \
+    X(ESME_EPI_NONE, 0, 1, 0, 0, 1, 1, 0) X(ESME_EPI_NONE, 16, 1, 0, 0, 1, 1, 0) X(ESME_EPI_NONE, 32, 1, 0, 0, 1, 1, 0) X(ESME_EPI_NONE, 64, 1, 0, 0, 1, 1, 0)  \
+    /* precision 'half', fp16 operands: fused rotary and SwiGLU LN-folded only; the residual epilogue on the fp16 pair stream (RP: resid / C = hi, lo pair_off   \
+       columns further) or on the fp32 stream (R32), with and without row statistics */                                                                         \
+    X(ESME_EPI_NONE, 0, 1, 0, 0, 0, 1, 0) X(ESME_EPI_NONE, 0, 0, 0, 0, 0, 1, 0) X(ESME_EPI_NONE, 16, 1, 0, 0, 0, 1, 0) X(ESME_EPI_NONE, 32, 1, 0, 0, 0, 1, 0)   \
+    X(ESME_EPI_NONE, 64, 1, 0, 0, 0, 1, 0) X(ESME_EPI_GELU, 0, 1, 0, 0, 0, 1, 0) X(ESME_EPI_GELU, 0, 0, 0, 0, 0, 1, 0) X(ESME_EPI_SWIGLU, 0, 1, 0, 0, 0, 1, 0)   \
+    X(ESME_EPI_RESIDUAL, 0, 0, 1, 0, 0, 1, 1) X(ESME_EPI_RESIDUAL, 0, 0, 0, 0, 0, 1, 1) X(ESME_EPI_RESIDUAL, 0, 0, 1, 1, 0, 1, 0) X(ESME_EPI_RESIDUAL, 0, 0, 0, 1, 0, 1, 0) \
+    /* bf16: every epilogue with and without LN fold; the residual epilogue with and without row statistics, on the fp32 (R32) or the bf16 stream */             \
+    X(ESME_EPI_NONE, 0, 1, 0, 0, 0, 0, 0) X(ESME_EPI_NONE, 0, 0, 0, 0, 0, 0, 0) X(ESME_EPI_NONE, 16, 1, 0, 0, 0, 0, 0) X(ESME_EPI_NONE, 16, 0, 0, 0, 0, 0, 0)   \
+    X(ESME_EPI_NONE, 32, 1, 0, 0, 0, 0, 0) X(ESME_EPI_NONE, 32, 0, 0, 0, 0, 0, 0) X(ESME_EPI_NONE, 64, 1, 0, 0, 0, 0, 0) X(ESME_EPI_NONE, 64, 0, 0, 0, 0, 0, 0) \
+    X(ESME_EPI_GELU, 0, 1, 0, 0, 0, 0, 0) X(ESME_EPI_GELU, 0, 0, 0, 0, 0, 0, 0) X(ESME_EPI_SWIGLU, 0, 1, 0, 0, 0, 0, 0) X(ESME_EPI_SWIGLU, 0, 0, 0, 0, 0, 0, 0) \
+    X(ESME_EPI_RESIDUAL, 0, 0, 1, 1, 0, 0, 0) X(ESME_EPI_RESIDUAL, 0, 0, 0, 1, 0, 0, 0) X(ESME_EPI_RESIDUAL, 0, 0, 1, 0, 0, 0, 0) X(ESME_EPI_RESIDUAL, 0, 0, 0, 0, 0, 0, 0)
+
+// Big tiles run one workgroup per CU (128 KB of LDS): once a launch is several rounds long, ONE persistent workgroup per CU walks
+// the tiles instead, fetching the next tile's first K-tile under the current epilogue.  The forms that have this persistent twin:
+//  - NOT fused rotary (the epilogue's tables + the address set-up spill), NOT the pair output;
+//  - NOT the pair-stream residual epilogue of precision 'half' (RP) since round 6 (tools/lab/pair_gemm_probe.py, profiles/r06_half_guard_regression.txt): the
+//    four registers of running column maxima the plan guard keeps in its store loop cost the PERSISTENT form 5 % of the whole launch once a workgroup walks
+//    >= 3 tiles (FFN-down 563 -> 590 us at M = 50 000; nothing at 1 or 2 rounds; the K loop is instruction-for-instruction the same and the loss is all
+//    SQ_WAIT_ANY), in every formulation tried and with the guard switched off at run time; the one-tile-per-workgroup form pays nothing for them and is as
+//    fast on this epilogue as the persistent form was without them (563 / 218 us against 563 / 219).
+constexpr bool has_persistent_twin(int bm, int bn, int rotd, bool pair, bool rp) { return bm == 256 && bn == 256 && rotd == 0 && !pair && !rp; }
+
+// The form of a call that esme_hip_gemm_bf16_opts has validated (rotd: the fused rotary's head dim or 0; lnf: LN fold; stats: row
+// statistics; the rest from `a`).  The rules:
+//  - fused rotary exists for the plain epilogue at head dims 16, 32 and 64;
+//  - pair_off means the fp16 pair STREAM under fp16's residual epilogue (RP), the pair OUTPUT under fp16's plain epilogue and under
+//    bf16's plain / GELU / SwiGLU epilogues (split-operand mode), and nothing under bf16's residual epilogue;
+//  - fp16's residual epilogue runs on the pair stream or else on the fp32 stream (R32); bf16's on the fp32 stream when resid32 is given;
+//  - only the residual epilogue emits row statistics, and it never folds a LayerNorm; neither does the bf16 pair output; the fp16
+//    pair output always does;
+//  - fp16 runs fused rotary and SwiGLU LayerNorm-folded only.
+// The first three refusals here, and launch_gemm's default, are defensive duplicates of checks the entry makes first: no call reaches them.
+static int gemm_form(GemmForm& f, const GemmArgs& a, int epi, int rotd, bool lnf, bool stats) {
+    if (epi < ESME_EPI_NONE || epi > ESME_EPI_SWIGLU) return fail(ESME_ERR_ARG, "gemm: unknown epilogue");
+    const bool plain = epi == ESME_EPI_NONE, resid = epi == ESME_EPI_RESIDUAL, f16 = a.f16 != 0, has_pair = a.pair_off != 0;
+    if (plain && rotd != 0 && rotd != 16 && rotd != 32 && rotd != 64) return fail(ESME_ERR_UNSUPPORTED, "gemm: fused rotary needs head dim 16, 32 or 64");
+    if (has_pair && !f16 && resid) return fail(ESME_ERR_ARG, "gemm: pair output does not combine with the residual epilogue");
+    f.epi = epi; f.rotd = plain ? rotd : 0; f.f16 = f16;
+    f.rp = f16 && has_pair && resid;
+    f.pair = has_pair && (f16 ? plain : !resid);
+    f.r32 = resid && !f.rp && (f16 || a.resid32);
+    f.stats = resid && stats;
+    f.lnf = !resid && (f.pair ? f16 : lnf);
+    if (f16 && !f.lnf && f.rotd) return fail(ESME_ERR_UNSUPPORTED, "gemm: fp16 fused rotary runs LayerNorm-folded only");
+    if (f16 && !f.lnf && epi == ESME_EPI_SWIGLU) return fail(ESME_ERR_UNSUPPORTED, "gemm: fp16 SwiGLU runs LayerNorm-folded only");
+    return ESME_OK;
+}
+
+// Choose the tile walk.  If the whole weight matrix fits an XCD's L2 (4 MB) next to the streaming activations, plain row-major order is
+// already optimal (W stays resident, every activation slab is fetched once).  Otherwise walk 8 x 4 groups (1 workgroup/CU, 32 CUs per
 // XCD): per group the XCD fetches 8 activation + 4 weight slabs instead of ~2 + all.
 template <int BM, int BN>
 static void set_raster(GemmArgs& a) {
@@ -1153,10 +1220,8 @@ static void set_raster(GemmArgs& a) {
     a.tiles_m = (int)((a.M + BM - 1) / BM);
     const double w_bytes = 2.0 * a.N * a.K;
     if (a.opt_gm > 0) { a.gm = a.opt_gm; a.gn = a.opt_gn > 0 ? a.opt_gn : a.tiles_n; }
-    else if (w_bytes <= 3.5e6 || a.tiles_n <= 6) { a.gm = 1; a.gn = a.tiles_n; }   // few columns: a row-major
-                                                                                     // wavefront is already a g x tiles_n group
-    else if (a.tiles_n % 5 == 0) { a.gm = 6; a.gn = 5; }                           // groups that tile the width evenly (N = 5 120: 20 columns):
-                                                                                     // no ragged last group; FFN-up -1.6 % vs 8 x 4
+    else if (w_bytes <= 3.5e6 || a.tiles_n <= 6) { a.gm = 1; a.gn = a.tiles_n; }   // few columns: a row-major wavefront is already a g x tiles_n group
+    else if (a.tiles_n % 5 == 0) { a.gm = 6; a.gn = 5; }     // groups that tile the width evenly (N = 5 120: 20 columns): no ragged last group; FFN-up -1.6 % vs 8 x 4
     else { a.gm = 8; a.gn = 4; }
     if (a.gn > a.tiles_n) a.gn = a.tiles_n;
     if (a.gm > a.tiles_m) a.gm = a.tiles_m;
@@ -1164,24 +1229,16 @@ static void set_raster(GemmArgs& a) {
     if (a.gn < 1) a.gn = 1;
 }
 
-template <int BM, int BN, int WM, int WN, int EPI, int ROTD, bool LNF, bool STATS, bool PERSIST = false, bool R32 = false, bool PAIR = false, bool F16 = false, bool RP = false>
+template <int BM, int BN, int WM, int WN, int EPI, int ROTD, bool LNF, bool STATS, bool R32, bool PAIR, bool F16, bool RP, bool PERSIST = false>
 static int launch_one(GemmArgs& a, hipStream_t s) {
     constexpr int smem = 2 * (BM + BN) * 128 + ((LNF || ROTD > 0) ? BM * 12 + BN * 8 : 0) + (STATS ? WN * BM * 8 : 0) + (RP ? 2 * BN * 8 : 0);
     set_raster<BM, BN>(a);
     int64_t blocks = (int64_t)a.tiles_m * a.tiles_n;
     if (blocks > 0x7fffffffLL) return fail(ESME_ERR_UNSUPPORTED, "gemm: grid too large");
-    if constexpr (!PERSIST && !PAIR && !RP && BM == 256 && BN == 256 && ROTD == 0) {     // (fused rotary: the epilogue's tables + the address set-up spill)
-        // Big tiles run one workgroup per CU (128 KB of LDS): once a launch is several rounds long, ONE persistent
-        // workgroup per CU walks the tiles instead, fetching the next tile's first K-tile under the current epilogue.
+    if constexpr (!PERSIST && has_persistent_twin(BM, BN, ROTD, PAIR, RP)) {
         const int ncu = cu_count() & ~7;
         const bool want = a.opt_persist < 0 ? persist_default() != 0 : a.opt_persist != 0;
-        // NOT the pair-stream residual epilogue of precision 'half' (RP) since round 6 (tools/lab/pair_gemm_probe.py, profiles/r06_half_guard_regression.txt): the
-        // four registers of running column maxima the plan guard keeps in its store loop cost the PERSISTENT form 5 % of the whole launch once a workgroup walks
-        // >= 3 tiles (FFN-down 563 -> 590 us at M = 50 000; nothing at 1 or 2 rounds; the K loop is instruction-for-instruction the same and the loss is all
-        // SQ_WAIT_ANY), in every formulation tried and with the guard switched off at run time; the one-tile-per-workgroup form pays nothing for them and is as
-        // fast on this epilogue as the persistent form was without them (563 / 218 us against 563 / 219).
-        if (want && a.vec_ok && ncu >= 8 && blocks >= 2 * (int64_t)ncu) return launch_one<BM, BN, WM, WN, EPI, ROTD, LNF, STATS, true, R32, false, F16, RP>(a, s);
-
+        if (want && a.vec_ok && ncu >= 8 && blocks >= 2 * (int64_t)ncu) return launch_one<BM, BN, WM, WN, EPI, ROTD, LNF, STATS, R32, PAIR, F16, RP, true>(a, s);
     }
     if constexpr (PERSIST) blocks = cu_count() & ~7;
     auto kern = gemm_bf16_kernel<BM, BN, WM, WN, EPI, ROTD, LNF, STATS, PERSIST, R32, PAIR, F16, RP>;
@@ -1194,98 +1251,27 @@ static int launch_one(GemmArgs& a, hipStream_t s) {
     return check_launch("gemm_bf16");
 }
 
-// epilogue x rotary-head-dim x LN-fold x row-stats dispatch for one tile configuration
+// one tile configuration: the launcher of the listed form (a form that is not listed cannot reach a launch)
 template <int BM, int BN, int WM, int WN>
-static int launch_gemm(GemmArgs& a, int epi, int rotd, bool lnf, bool stats, hipStream_t s) {
-#define ESME_L(E, R, L, S) launch_one<BM, BN, WM, WN, E, R, L, S>(a, s)
-    if (a.pair_off && !a.f16) {                     // split-operand mode: (hi, lo) pair output (checked by the caller: no LN fold, no residual)
-#define ESME_LP(E, R) launch_one<BM, BN, WM, WN, E, R, false, false, false, false, true>(a, s)
-        switch (epi) {
-            case ESME_EPI_NONE:
-                switch (rotd) {
-                    case 0: return ESME_LP(ESME_EPI_NONE, 0);
-                    case 16: return ESME_LP(ESME_EPI_NONE, 16);
-                    case 32: return ESME_LP(ESME_EPI_NONE, 32);
-                    case 64: return ESME_LP(ESME_EPI_NONE, 64);
-                    default: return fail(ESME_ERR_UNSUPPORTED, "gemm: fused rotary needs head dim 16, 32 or 64");
-                }
-            case ESME_EPI_GELU: return ESME_LP(ESME_EPI_GELU, 0);
-            case ESME_EPI_SWIGLU: return ESME_LP(ESME_EPI_SWIGLU, 0);
-            default: return fail(ESME_ERR_ARG, "gemm: pair output does not combine with the residual epilogue");
-        }
-#undef ESME_LP
+static int launch_gemm(GemmArgs& a, const GemmForm& f, hipStream_t s) {
+    switch (f.key()) {
+#define ESME_GEMM_CASE(E, R, L, S, R32, P, H, RP) \
+        case GemmForm{E, R, L, S, R32, P, H, RP}.key(): return launch_one<BM, BN, WM, WN, E, R, L, S, R32, P, H, RP>(a, s);
+        ESME_GEMM_FORMS(ESME_GEMM_CASE)
+#undef ESME_GEMM_CASE
+        default: return fail(ESME_ERR_UNSUPPORTED, "gemm: this combination of epilogue and fusions is not built");
     }
-    if (a.f16 && a.pair_off && epi == ESME_EPI_NONE) {   // precision 'half', q / k as pairs: the LN-folded projection writes (hi, lo), rotated with fp32 tables (checked by the caller)
-        switch (rotd) {
-            case 0: return launch_one<BM, BN, WM, WN, ESME_EPI_NONE, 0, true, false, false, false, true, true>(a, s);
-            case 16: return launch_one<BM, BN, WM, WN, ESME_EPI_NONE, 16, true, false, false, false, true, true>(a, s);
-            case 32: return launch_one<BM, BN, WM, WN, ESME_EPI_NONE, 32, true, false, false, false, true, true>(a, s);
-            case 64: return launch_one<BM, BN, WM, WN, ESME_EPI_NONE, 64, true, false, false, false, true, true>(a, s);
-            default: return fail(ESME_ERR_UNSUPPORTED, "gemm: fused rotary needs head dim 16, 32 or 64");
-        }
-    }
-    if (a.f16) {                                    // precision 'half': fp16 operands (checked by the caller: residual epilogue only on the fp32 stream)
-#define ESME_LH(E, R, L, S, R32) launch_one<BM, BN, WM, WN, E, R, L, S, false, R32, false, true>(a, s)
-        switch (epi) {
-            case ESME_EPI_NONE:
-                switch (rotd) {
-                    case 0: return lnf ? ESME_LH(ESME_EPI_NONE, 0, true, false, false) : ESME_LH(ESME_EPI_NONE, 0, false, false, false);
-                    case 16: return lnf ? ESME_LH(ESME_EPI_NONE, 16, true, false, false) : fail(ESME_ERR_UNSUPPORTED, "gemm: fp16 fused rotary runs LayerNorm-folded only");
-                    case 32: return lnf ? ESME_LH(ESME_EPI_NONE, 32, true, false, false) : fail(ESME_ERR_UNSUPPORTED, "gemm: fp16 fused rotary runs LayerNorm-folded only");
-                    case 64: return lnf ? ESME_LH(ESME_EPI_NONE, 64, true, false, false) : fail(ESME_ERR_UNSUPPORTED, "gemm: fp16 fused rotary runs LayerNorm-folded only");
-                    default: return fail(ESME_ERR_UNSUPPORTED, "gemm: fused rotary needs head dim 16, 32 or 64");
-                }
-            case ESME_EPI_GELU: return lnf ? ESME_LH(ESME_EPI_GELU, 0, true, false, false) : ESME_LH(ESME_EPI_GELU, 0, false, false, false);
-            case ESME_EPI_SWIGLU: return lnf ? ESME_LH(ESME_EPI_SWIGLU, 0, true, false, false) : fail(ESME_ERR_UNSUPPORTED, "gemm: fp16 SwiGLU runs LayerNorm-folded only");
-            case ESME_EPI_RESIDUAL:
-                if (a.pair_off)                      // the stream as an fp16 pair (resid / C = hi, lo pair_off columns further)
-                    return stats ? launch_one<BM, BN, WM, WN, ESME_EPI_RESIDUAL, 0, false, true, false, false, false, true, true>(a, s)
-                                 : launch_one<BM, BN, WM, WN, ESME_EPI_RESIDUAL, 0, false, false, false, false, false, true, true>(a, s);
-                return stats ? ESME_LH(ESME_EPI_RESIDUAL, 0, false, true, true) : ESME_LH(ESME_EPI_RESIDUAL, 0, false, false, true);
-            default: return fail(ESME_ERR_ARG, "gemm: unknown epilogue");
-        }
-#undef ESME_LH
-    }
-    switch (epi) {
-        case ESME_EPI_NONE:
-            switch (rotd) {
-                case 0: return lnf ? ESME_L(ESME_EPI_NONE, 0, true, false) : ESME_L(ESME_EPI_NONE, 0, false, false);
-                case 16: return lnf ? ESME_L(ESME_EPI_NONE, 16, true, false) : ESME_L(ESME_EPI_NONE, 16, false, false);
-                case 32: return lnf ? ESME_L(ESME_EPI_NONE, 32, true, false) : ESME_L(ESME_EPI_NONE, 32, false, false);
-                case 64: return lnf ? ESME_L(ESME_EPI_NONE, 64, true, false) : ESME_L(ESME_EPI_NONE, 64, false, false);
-                default: return fail(ESME_ERR_UNSUPPORTED, "gemm: fused rotary needs head dim 16, 32 or 64");
-            }
-        case ESME_EPI_GELU: return lnf ? ESME_L(ESME_EPI_GELU, 0, true, false) : ESME_L(ESME_EPI_GELU, 0, false, false);
-        case ESME_EPI_SWIGLU: return lnf ? ESME_L(ESME_EPI_SWIGLU, 0, true, false) : ESME_L(ESME_EPI_SWIGLU, 0, false, false);
-        case ESME_EPI_RESIDUAL:
-            if (a.resid32) return stats ? launch_one<BM, BN, WM, WN, ESME_EPI_RESIDUAL, 0, false, true, false, true>(a, s)
-                                        : launch_one<BM, BN, WM, WN, ESME_EPI_RESIDUAL, 0, false, false, false, true>(a, s);
-            return stats ? ESME_L(ESME_EPI_RESIDUAL, 0, false, true) : ESME_L(ESME_EPI_RESIDUAL, 0, false, false);
-        default: return fail(ESME_ERR_ARG, "gemm: unknown epilogue");
-    }
-#undef ESME_L
 }
 
 }  // namespace esme
 
 using namespace esme;
 
-// compute units of the current device (cached per device ordinal; 256 on MI355X)
-static int esme::cu_count() {
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int v = cached[dev & 63].load(std::memory_order_relaxed);
-    if (v <= 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cached[dev & 63].store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
 #ifdef ESME_GEMM_TRACE
 // Instrumented build only (make TRACE=1 -> libesme_hip_trace.so, tools/gemm_phase_trace.py): never in the shipped library.
-extern "C" void esme_hip_debug_set_gemm_nt(int v) { esme::g_nt_store = v; }
-extern "C" void esme_hip_debug_set_gemm_stagger(int v) { esme::g_stagger = v; }
+static int g_nt_store = 0, g_stagger = 0;          // timing experiments
+extern "C" void esme_hip_debug_set_gemm_nt(int v) { g_nt_store = v; }
+extern "C" void esme_hip_debug_set_gemm_stagger(int v) { g_stagger = v; }
 static unsigned long long* g_trace = nullptr;
 extern "C" void esme_hip_debug_set_gemm_trace(void* p) { g_trace = (unsigned long long*)p; }
 #endif
@@ -1306,9 +1292,47 @@ extern "C" int esme_hip_gemm_stats_blocks_opts(int64_t M, int N, const esme_gemm
 }
 extern "C" int esme_hip_gemm_stats_blocks(int64_t M, int N) { return esme_hip_gemm_stats_blocks_opts(M, N, nullptr); }
 
+// Column split of a residual GEMM whose width ends in a half-empty 256-column tile (round 6: ESMC-600M, N = 1 152 = 4.5 tiles -- a tenth of the launch's
+// MFMAs multiply padding, and 126 x 5 = 630 tiles are 2.46 rounds of the 256 CUs where 126 x 4 = 504 are 1.97).  When dropping that column of tiles saves a
+// whole round, the full tiles run as before and the last 128 columns go to the 128 x 128 configuration in a second launch on offset pointers.  Same bits:
+// every output element sums its K-tiles in the same order in both configurations, and a 128-wide statistics partial (w0 + w1) is what the half-empty
+// 256-wide tile emitted ((w0 + w1) + (0 + 0)).  Only with the heuristic tile choice (an explicit esme_gemm_opts_t.tile gets exactly that configuration).
+// MEASURED (tools/gemm_colsplit_ab.py, profiles/r06_gemm_colsplit_ab.txt, M = 32 064): the round arithmetic does not hold on this power-capped part -- bf16
+// out-projection 97.3 -> 98.1 us, FFN-down 207.2 -> 213.7 us (the "2.46 rounds" launch already costs 2.46, not 3, tile times); only the fp16 PAIR-stream
+// epilogue, whose tile seam is the expensive one, gains (FFN-down 255.9 -> 244.1 us, out-projection 119.8 = 119.8): the split is taken there only.
+static bool column_split_pays(const GemmArgs& a, const GemmForm& f, const esme_gemm_opts_t* opts) {
+    if (!f.rp || (opts && opts->tile) || a.N <= 256 || a.N % 256 != 128) return false;
+    const int64_t tm = (a.M + 255) / 256, ncu = cu_count() & ~7;
+    const int64_t full = tm * ((a.N + 255) / 256), main_tiles = tm * (a.N / 256);
+    return ncu >= 8 && main_tiles >= 160 && (main_tiles + ncu - 1) / ncu < (full + ncu - 1) / ncu;
+}
+
+// the launch of columns [c0, c0 + 128) of `a`: every per-column operand moves with them
+static GemmArgs last_columns(const GemmArgs& a, int c0) {
+    GemmArgs t = a;
+    t.N = 128;
+    t.W = a.W + (int64_t)c0 * (a.kt_wrap > 0 ? a.kt_wrap * BK : a.K);
+    t.C = a.C + c0;
+    if (a.bias) t.bias = a.bias + c0;
+    if (a.resid) t.resid = a.resid + c0;
+    if (a.resid32) t.resid32 = a.resid32 + c0;
+    if (a.ps_in) t.ps_in = a.ps_in + c0;
+    if (a.ps_out) t.ps_out = a.ps_out + c0;
+    if (a.col_absmax) t.col_absmax = a.col_absmax + c0;
+    if (a.stats_out) t.stats_out = a.stats_out + 2 * (int64_t)(c0 / 256) * a.stat_ld;
+    if (a.ext_off) { t.ext_base = c0; t.ext_off = a.ext_off - c0; }
+    return t;
+}
+
+// What f16, pair_off, w_k and c32 make of a call; each mode owns the checks of its fields.  kSplitOperand ('exact'): A = [hi | lo]
+// against one W (w_k), (hi, lo) bf16 pair output (pair_off), fp32 output (c32).  Precision 'half' (fp16 A, W, tables, C): kF16; kF16PairOut, q / k as
+// pairs: pair output of the LN-folded plain projection; kF16PairStream: the residual stream as an fp16 pair [hi | lo].
+enum GemmMode { kBf16, kSplitOperand, kF16, kF16PairOut, kF16PairStream };
+
 extern "C" int esme_hip_gemm_bf16_opts(const void* A, int64_t lda, const void* W, const void* bias, const void* resid,
                                        int64_t ldr, void* C, int64_t ldc, int64_t M, int N, int K, int epilogue,
                                        float alpha, const esme_gemm_fusion_t* fu, const esme_gemm_opts_t* opts, void* stream) {
+    auto aligned = [](const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; };
     ESME_CHECK_ARG(!opts || (opts->struct_bytes == (int)sizeof(esme_gemm_opts_t) && opts->tile >= 0 && opts->tile <= 2),
                    "gemm: options struct of another ABI or bad tile");
     ESME_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm: bad sizes");
@@ -1316,86 +1340,96 @@ extern "C" int esme_hip_gemm_bf16_opts(const void* A, int64_t lda, const void* W
     if (M == 0) return ESME_OK;
     ESME_CHECK_ARG(A && W && C, "gemm: null pointer");
     if (K % BK != 0) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: K must be a multiple of 64");
-    const int n_out = epilogue == ESME_EPI_SWIGLU ? N / 2 : N;
-    if (epilogue == ESME_EPI_SWIGLU && N % 64 != 0) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: swiglu needs N % 64 == 0");
+    const bool plain = epilogue == ESME_EPI_NONE, residual = epilogue == ESME_EPI_RESIDUAL, swiglu = epilogue == ESME_EPI_SWIGLU;
+    const int n_out = swiglu ? N / 2 : N;
+    if (swiglu && N % 64 != 0) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: swiglu needs N % 64 == 0");
     ESME_CHECK_ARG(lda >= K && lda % 8 == 0 && ldc >= n_out, "gemm: bad lda/ldc");
     ESME_CHECK_ARG(aligned16(A) && aligned16(W), "gemm: A and W must be 16-byte aligned");
-    ESME_CHECK_ARG(!bias || (reinterpret_cast<uintptr_t>(bias) & 7u) == 0, "gemm: misaligned bias");
+    ESME_CHECK_ARG(!bias || aligned(bias, 8), "gemm: misaligned bias");
     // The coalesced epilogue stores 16 B per lane: it needs ldc % 8 == 0, a 16-B aligned C and
     // N % 8 == 0; otherwise (e.g. the (T, 33) vocab projection) it falls back to 2-byte accesses.
-    int vec_ok = (ldc % 8 == 0) && aligned16(C) && (n_out % 8 == 0) && N >= 8;
+    bool vec_ok = (ldc % 8 == 0) && aligned16(C) && (n_out % 8 == 0) && N >= 8;
     const bool r32 = fu && fu->resid32;
     if (r32) {
-        ESME_CHECK_ARG(epilogue == ESME_EPI_RESIDUAL, "gemm: resid32 belongs to the residual epilogue");
+        ESME_CHECK_ARG(residual, "gemm: resid32 belongs to the residual epilogue");
         ESME_CHECK_ARG(fu->ld32 >= N && fu->ld32 % 4 == 0 && aligned16(fu->resid32), "gemm: resid32 needs ld32 >= N, ld32 % 4 == 0, 16-byte alignment");
         if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: the fp32 residual stream needs a 16-byte addressable C and N % 8 == 0");
-    } else if (epilogue == ESME_EPI_RESIDUAL) {
+    } else if (residual) {
         ESME_CHECK_ARG(resid && ldr >= N, "gemm: residual epilogue needs resid with ldr >= N");
-        vec_ok = vec_ok && (ldr % 8 == 0) && aligned16(resid) && N >= 8;
+        vec_ok = vec_ok && (ldr % 8 == 0) && aligned16(resid);
     }
-    if (epilogue == ESME_EPI_SWIGLU && !vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: swiglu needs ldc % 8 == 0 and a 16-byte aligned C");
-    GemmArgs a{(const u16*)A, lda, (const u16*)W, (const u16*)bias, (const u16*)resid, ldr, (u16*)C, ldc, M, N, K, alpha, 0, vec_ok,
-               nullptr, nullptr, nullptr, 0, 0, 0, 1, 1, 0, 0, nullptr, 0, 0, 0.f, nullptr, nullptr, nullptr};
+    if (swiglu && !vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: swiglu needs ldc % 8 == 0 and a 16-byte aligned C");
+
+    GemmArgs a{};
+    a.A = (const u16*)A; a.lda = lda; a.W = (const u16*)W; a.bias = (const u16*)bias; a.resid = (const u16*)resid; a.ldr = ldr;
+    a.C = (u16*)C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.alpha = alpha; a.vec_ok = vec_ok; a.stat_ld = M;
 #ifdef ESME_GEMM_TRACE
     a.nt_store = g_nt_store; a.stagger = g_stagger; a.trace = g_trace;
 #endif
     if (opts) { a.opt_gm = opts->raster_gm; a.opt_gn = opts->raster_gn; a.opt_persist = opts->persist; }
+    if (r32) { a.resid32 = fu->resid32; a.ld32 = fu->ld32; }
     int rotd = 0;
     bool lnf = false, stats = false;
-    if (r32) { a.resid32 = fu->resid32; a.ld32 = fu->ld32; }
-    ESME_CHECK_ARG(!fu || (!fu->pair_scale_in && !fu->pair_scale_out && !fu->ext_off) || (fu->f16 && fu->pair_off && epilogue == ESME_EPI_RESIDUAL),
-                   "gemm: pair_scale_in / pair_scale_out / ext_* belong to the fp16 pair stream's residual epilogue");
-    ESME_CHECK_ARG(!fu || !fu->pair_cols || (fu->f16 && fu->pair_off && epilogue == ESME_EPI_NONE), "gemm: pair_cols belongs to the fp16 pair output");
-    ESME_CHECK_ARG(!fu || !fu->col_absmax || (fu->f16 && fu->pair_off && epilogue == ESME_EPI_RESIDUAL), "gemm: col_absmax belongs to the fp16 pair stream's residual epilogue");
-    ESME_CHECK_ARG(!fu || !fu->qk_sumsq || (fu->f16 && fu->ln_partial && fu->head_dim != 0 && !fu->pair_off), "gemm: qk_sumsq belongs to the fp16 LN-folded projection with fused rotary (single output)");
-    if (fu && fu->f16 && fu->pair_off && epilogue == ESME_EPI_NONE) {   // precision 'half', q / k as pairs: pair output of the LN-folded plain projection
-        ESME_CHECK_ARG(fu->ln_partial && !r32 && !fu->w_k && !fu->c32 && !fu->stats_out, "gemm: the fp16 pair output belongs to the LN-folded plain epilogue");
-        ESME_CHECK_ARG(fu->pair_off >= N && fu->pair_off % 8 == 0 && ldc >= fu->pair_off + (fu->pair_cols > 0 ? fu->pair_cols : N) && fu->pair_cols >= 0 && fu->pair_cols % 256 == 0,
-                       "gemm: pair_off must be a multiple of 8 with N <= pair_off and room for the lo columns; pair_cols a multiple of 256");
-        if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: pair output needs a 16-byte addressable C and N % 8 == 0");
-        a.pair_off = fu->pair_off; a.pair_cols = fu->pair_cols;
-    } else if (fu && fu->f16 && fu->pair_off) {                      // precision 'half': the residual stream as an fp16 pair [hi | lo]
-        ESME_CHECK_ARG(epilogue == ESME_EPI_RESIDUAL && !r32 && !fu->w_k && !fu->c32 && !fu->ln_partial, "gemm: the fp16 pair stream belongs to the residual epilogue");
-        ESME_CHECK_ARG(fu->pair_off >= N && fu->pair_off % 8 == 0 && ldc >= fu->pair_off + N && ldr >= fu->pair_off + N,
-                       "gemm: pair_off must be a multiple of 8 with N <= pair_off <= ldc - N, ldr - N");
-        if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: the pair stream needs 16-byte addressable rows and N % 8 == 0");
-        a.pair_off = fu->pair_off;
-        ESME_CHECK_ARG((!fu->pair_scale_in || aligned16(fu->pair_scale_in)) && (!fu->pair_scale_out || aligned16(fu->pair_scale_out)) && (N % 4 == 0),
-                       "gemm: pair_scale_in / pair_scale_out must be 16-byte aligned float (N) vectors");
-        a.ps_in = fu->pair_scale_in; a.ps_out = fu->pair_scale_out;
-        if (fu->ext_off) {
-            ESME_CHECK_ARG(fu->ext_off >= N && fu->ext_off + 64 <= fu->pair_off && fu->ext_n >= 0 && fu->ext_n <= 64 && (fu->ext_n == 0 || fu->ext_sel),
-                           "gemm: the extension tile is 64 columns between hi and lo (N <= ext_off, ext_off + 64 <= pair_off) with <= 64 selected columns");
-            a.ext_sel = fu->ext_sel; a.ext_n = fu->ext_n; a.ext_off = fu->ext_off;
-        }
-        ESME_CHECK_ARG(!fu->col_absmax || (reinterpret_cast<uintptr_t>(fu->col_absmax) & 3u) == 0, "gemm: misaligned col_absmax");
-        a.col_absmax = fu->col_absmax;
-    } else if (fu && (fu->w_k || fu->pair_off || fu->c32)) {        // split-operand ('exact') mode
-        if (fu->w_k) {
-            ESME_CHECK_ARG(fu->w_k > 0 && fu->w_k % BK == 0 && (K == fu->w_k || K == 2 * fu->w_k), "gemm: w_k (the K of W) must be a multiple of 64 with K = w_k or K = 2 w_k (the K-tile index of W wraps once)");
-            if (fu->w_k < K) a.kt_wrap = fu->w_k / BK;
-        }
-        if (fu->pair_off) {
-            ESME_CHECK_ARG(epilogue != ESME_EPI_RESIDUAL && !fu->ln_partial && !fu->stats_out, "gemm: pair output belongs to the plain / GELU / SwiGLU epilogues without LN fold");
-            ESME_CHECK_ARG(fu->pair_off >= n_out && fu->pair_off % 8 == 0 && ldc >= fu->pair_off + n_out, "gemm: pair_off must be a multiple of 8 with n_out <= pair_off <= ldc - n_out");
-            if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: pair output needs a 16-byte addressable C and N % 8 == 0");
-            a.pair_off = fu->pair_off;
-        }
-        if (fu->c32) {
-            ESME_CHECK_ARG(!fu->pair_off && epilogue != ESME_EPI_SWIGLU && fu->ldc32 >= N && (reinterpret_cast<uintptr_t>(fu->c32) & 3u) == 0, "gemm: c32 needs ldc32 >= N, no pair output, no SwiGLU");
-            a.c32 = fu->c32; a.ldc32 = fu->ldc32;
-            a.vec_ok = 0;                                            // fp32 results leave through the scalar store path
-        }
-    }
-    if (fu && fu->f16) {                                             // precision 'half': fp16 A, W, tables, C
-        ESME_CHECK_ARG(!fu->w_k && !fu->c32 && (!fu->pair_off || epilogue == ESME_EPI_RESIDUAL || epilogue == ESME_EPI_NONE), "gemm: fp16 operands do not combine with the split-operand fields");
-        ESME_CHECK_ARG(epilogue != ESME_EPI_RESIDUAL || r32 || fu->pair_off, "gemm: fp16 operands run the residual epilogue on the fp32 stream or the fp16 pair stream");
-        if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: fp16 operands need a 16-byte addressable C and N % 8 == 0");
-        a.f16 = 1;
-    }
     if (fu) {
+        const GemmMode mode = fu->f16 && fu->pair_off ? (plain ? kF16PairOut : kF16PairStream)
+                              : (fu->w_k || fu->pair_off || fu->c32) ? kSplitOperand : fu->f16 ? kF16 : kBf16;
+        // the fields that belong to one mode
+        ESME_CHECK_ARG((!fu->pair_scale_in && !fu->pair_scale_out && !fu->ext_off) || (mode == kF16PairStream && residual),
+                       "gemm: pair_scale_in / pair_scale_out / ext_* belong to the fp16 pair stream's residual epilogue");
+        ESME_CHECK_ARG(!fu->pair_cols || mode == kF16PairOut, "gemm: pair_cols belongs to the fp16 pair output");
+        ESME_CHECK_ARG(!fu->col_absmax || (mode == kF16PairStream && residual), "gemm: col_absmax belongs to the fp16 pair stream's residual epilogue");
+        ESME_CHECK_ARG(!fu->qk_sumsq || (fu->f16 && fu->ln_partial && fu->head_dim != 0 && !fu->pair_off), "gemm: qk_sumsq belongs to the fp16 LN-folded projection with fused rotary (single output)");
+        switch (mode) {
+            case kF16PairOut:
+                ESME_CHECK_ARG(fu->ln_partial && !r32 && !fu->w_k && !fu->c32 && !fu->stats_out, "gemm: the fp16 pair output belongs to the LN-folded plain epilogue");
+                ESME_CHECK_ARG(fu->pair_off >= N && fu->pair_off % 8 == 0 && ldc >= fu->pair_off + (fu->pair_cols > 0 ? fu->pair_cols : N) && fu->pair_cols >= 0 && fu->pair_cols % 256 == 0,
+                               "gemm: pair_off must be a multiple of 8 with N <= pair_off and room for the lo columns; pair_cols a multiple of 256");
+                if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: pair output needs a 16-byte addressable C and N % 8 == 0");
+                a.pair_cols = fu->pair_cols;
+                break;
+            case kF16PairStream:
+                ESME_CHECK_ARG(residual && !r32 && !fu->w_k && !fu->c32 && !fu->ln_partial, "gemm: the fp16 pair stream belongs to the residual epilogue");
+                ESME_CHECK_ARG(fu->pair_off >= N && fu->pair_off % 8 == 0 && ldc >= fu->pair_off + N && ldr >= fu->pair_off + N,
+                               "gemm: pair_off must be a multiple of 8 with N <= pair_off <= ldc - N, ldr - N");
+                if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: the pair stream needs 16-byte addressable rows and N % 8 == 0");
+                ESME_CHECK_ARG((!fu->pair_scale_in || aligned16(fu->pair_scale_in)) && (!fu->pair_scale_out || aligned16(fu->pair_scale_out)) && (N % 4 == 0),
+                               "gemm: pair_scale_in / pair_scale_out must be 16-byte aligned float (N) vectors");
+                a.ps_in = fu->pair_scale_in; a.ps_out = fu->pair_scale_out;
+                if (fu->ext_off) {
+                    ESME_CHECK_ARG(fu->ext_off >= N && fu->ext_off + 64 <= fu->pair_off && fu->ext_n >= 0 && fu->ext_n <= 64 && (fu->ext_n == 0 || fu->ext_sel),
+                                   "gemm: the extension tile is 64 columns between hi and lo (N <= ext_off, ext_off + 64 <= pair_off) with <= 64 selected columns");
+                    a.ext_sel = fu->ext_sel; a.ext_n = fu->ext_n; a.ext_off = fu->ext_off;
+                }
+                ESME_CHECK_ARG(!fu->col_absmax || aligned(fu->col_absmax, 4), "gemm: misaligned col_absmax");
+                a.col_absmax = fu->col_absmax;
+                break;
+            case kSplitOperand:
+                if (fu->w_k) {
+                    ESME_CHECK_ARG(fu->w_k > 0 && fu->w_k % BK == 0 && (K == fu->w_k || K == 2 * fu->w_k), "gemm: w_k (the K of W) must be a multiple of 64 with K = w_k or K = 2 w_k (the K-tile index of W wraps once)");
+                    if (fu->w_k < K) a.kt_wrap = fu->w_k / BK;
+                }
+                if (fu->pair_off) {
+                    ESME_CHECK_ARG(!residual && !fu->ln_partial && !fu->stats_out, "gemm: pair output belongs to the plain / GELU / SwiGLU epilogues without LN fold");
+                    ESME_CHECK_ARG(fu->pair_off >= n_out && fu->pair_off % 8 == 0 && ldc >= fu->pair_off + n_out, "gemm: pair_off must be a multiple of 8 with n_out <= pair_off <= ldc - n_out");
+                    if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: pair output needs a 16-byte addressable C and N % 8 == 0");
+                }
+                if (fu->c32) {
+                    ESME_CHECK_ARG(!fu->pair_off && !swiglu && fu->ldc32 >= N && aligned(fu->c32, 4), "gemm: c32 needs ldc32 >= N, no pair output, no SwiGLU");
+                    a.c32 = fu->c32; a.ldc32 = fu->ldc32;
+                    a.vec_ok = 0;                                        // fp32 results leave through the scalar store path
+                }
+                ESME_CHECK_ARG(!fu->f16, "gemm: fp16 operands do not combine with the split-operand fields");
+                break;
+            case kF16:
+                ESME_CHECK_ARG(!residual || r32, "gemm: fp16 operands run the residual epilogue on the fp32 stream or the fp16 pair stream");
+                if (!vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: fp16 operands need a 16-byte addressable C and N % 8 == 0");
+                break;
+            case kBf16: break;
+        }
+        a.pair_off = fu->pair_off;
+        a.f16 = fu->f16 != 0;
         if (fu->head_dim != 0) {                                     // fused rotary
-            ESME_CHECK_ARG(epilogue == ESME_EPI_NONE, "gemm: fused rotary needs ESME_EPI_NONE");
+            ESME_CHECK_ARG(plain, "gemm: fused rotary needs ESME_EPI_NONE");
             ESME_CHECK_ARG(fu->cos && fu->sin && fu->pos && fu->max_len > 0, "gemm: fused rotary needs cos, sin, pos, max_len");
             if (fu->head_dim != 16 && fu->head_dim != 32 && fu->head_dim != 64)
                 ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: fused rotary needs head dim 16, 32 or 64 (use esme_hip_rotary_varlen otherwise)");
@@ -1412,72 +1446,39 @@ extern "C" int esme_hip_gemm_bf16_opts(const void* A, int64_t lda, const void* W
             }
         }
         if (fu->ln_partial) {                                        // LayerNorm folded into this GEMM
-            ESME_CHECK_ARG(epilogue != ESME_EPI_RESIDUAL, "gemm: LN fold does not combine with the residual epilogue");
-            ESME_CHECK_ARG(fu->ln_c1 && fu->ln_c2 && aligned16(fu->ln_c1) && aligned16(fu->ln_c2) &&
-                           (reinterpret_cast<uintptr_t>(fu->ln_partial) & 7u) == 0 && fu->ln_nblk > 0 && fu->ln_dim > 0,
+            ESME_CHECK_ARG(!residual, "gemm: LN fold does not combine with the residual epilogue");
+            ESME_CHECK_ARG(fu->ln_c1 && fu->ln_c2 && aligned16(fu->ln_c1) && aligned16(fu->ln_c2) && aligned(fu->ln_partial, 8) && fu->ln_nblk > 0 && fu->ln_dim > 0,
                            "gemm: LN fold needs 16-byte aligned c1, c2, 8-byte aligned partial sums, ln_nblk > 0, ln_dim > 0");
             if (N % 4 != 0 || !vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: LN fold needs N % 4 == 0 and 16-byte addressable C");
             a.ln_partial = fu->ln_partial; a.ln_nblk = fu->ln_nblk; a.ln_dim = fu->ln_dim; a.ln_eps = fu->ln_eps;
             a.ln_c1 = fu->ln_c1; a.ln_c2 = fu->ln_c2;
             a.ovf = fu->overflow_flag;
             lnf = true;
-            if (fu->qk_sumsq) {
-                ESME_CHECK_ARG(fu->f16 && fu->head_dim != 0 && !fu->pair_off && (reinterpret_cast<uintptr_t>(fu->qk_sumsq) & 3u) == 0,
-                               "gemm: qk_sumsq belongs to the fp16 LN-folded projection with fused rotary and a single (non-pair) output");
-                a.qk_sumsq = fu->qk_sumsq;
-            }
+            // (whose field it is was checked above: what is left of this check is the alignment; the text is the entry's historical one)
+            ESME_CHECK_ARG(!fu->qk_sumsq || aligned(fu->qk_sumsq, 4), "gemm: qk_sumsq belongs to the fp16 LN-folded projection with fused rotary and a single (non-pair) output");
+            a.qk_sumsq = fu->qk_sumsq;
         }
         if (fu->stats_out) {                                         // emit row statistics for the next LayerNorm
-            ESME_CHECK_ARG(epilogue == ESME_EPI_RESIDUAL, "gemm: row statistics are emitted by the residual epilogue");
+            ESME_CHECK_ARG(residual, "gemm: row statistics are emitted by the residual epilogue");
             if (N % 64 != 0 || !vec_ok) ESME_FAIL(ESME_ERR_UNSUPPORTED, "gemm: row statistics need N % 64 == 0 and 16-byte addressable C");
-            ESME_CHECK_ARG((reinterpret_cast<uintptr_t>(fu->stats_out) & 7u) == 0, "gemm: misaligned stats_out");
+            ESME_CHECK_ARG(aligned(fu->stats_out, 8), "gemm: misaligned stats_out");
             a.stats_out = fu->stats_out;
             stats = true;
         }
     }
+    // bytes this launch writes: C (16-bit) [+ its lo half] [+ the fp32 stream]; past the memory-side cache they leave with the non-temporal hint
+    a.stream_out = (double)M * n_out * 2.0 * (a.pair_off ? 2.0 : 1.0) + (a.resid32 ? (double)M * N * 4.0 : 0.0) > kNtMinMB * 1048576.0;
+    GemmForm f{};
+    if (const int rc = gemm_form(f, a, epilogue, rotd, lnf, stats)) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    a.stat_ld = M;
-    {   // bytes this launch writes: C (16-bit) [+ its lo half] [+ the fp32 stream]
-        const double out_bytes = (double)M * n_out * 2.0 * (a.pair_off ? 2.0 : 1.0) + (a.resid32 ? (double)M * N * 4.0 : 0.0);
-        a.stream_out = out_bytes > kNtMinMB * 1048576.0;
+    if (pick_tile(M, N, opts) == 1) return launch_gemm<128, 128, 2, 2>(a, f, s);
+    if (column_split_pays(a, f, opts)) {
+        GemmArgs full_tiles = a, last = last_columns(a, N - 128);
+        full_tiles.N = N - 128;
+        if (const int rc = launch_gemm<256, 256, 2, 4>(full_tiles, f, s)) return rc;
+        return launch_gemm<128, 128, 2, 2>(last, f, s);
     }
-    const int tile = pick_tile(M, N, opts);
-    if (tile == 1) return launch_gemm<128, 128, 2, 2>(a, epilogue, rotd, lnf, stats, s);
-    // Column split of a residual GEMM whose width ends in a half-empty 256-column tile (round 6: ESMC-600M, N = 1 152 = 4.5 tiles -- a tenth of the launch's
-    // MFMAs multiply padding, and 126 x 5 = 630 tiles are 2.46 rounds of the 256 CUs where 126 x 4 = 504 are 1.97).  When dropping that column of tiles saves a
-    // whole round, the full tiles run as before and the last 128 columns go to the 128 x 128 configuration in a second launch on offset pointers.  Same bits:
-    // every output element sums its K-tiles in the same order in both configurations, and a 128-wide statistics partial (w0 + w1) is what the half-empty
-    // 256-wide tile emitted ((w0 + w1) + (0 + 0)).  Only with the heuristic tile choice (an explicit esme_gemm_opts_t.tile gets exactly that configuration).
-    // MEASURED (tools/gemm_colsplit_ab.py, profiles/r06_gemm_colsplit_ab.txt, M = 32 064): the round arithmetic does not hold on this power-capped part -- bf16
-    // out-projection 97.3 -> 98.1 us, FFN-down 207.2 -> 213.7 us (the "2.46 rounds" launch already costs 2.46, not 3, tile times); only the fp16 PAIR-stream
-    // epilogue, whose tile seam is the expensive one, gains (FFN-down 255.9 -> 244.1 us, out-projection 119.8 = 119.8): the split is taken there only.
-    if (epilogue == ESME_EPI_RESIDUAL && a.f16 && a.pair_off && !(opts && opts->tile) && N > 256 && N % 256 == 128 && vec_ok && !a.c32) {
-        const int64_t tm = (M + 255) / 256, ncu = cu_count() & ~7;
-        const int64_t full = tm * ((N + 255) / 256), main_tiles = tm * (N / 256);
-        if (ncu >= 8 && main_tiles >= 160 && (main_tiles + ncu - 1) / ncu < (full + ncu - 1) / ncu) {
-            const int c0 = N - 128;
-            GemmArgs a1 = a, a2 = a;
-            a1.N = c0;
-            const int rc1 = launch_gemm<256, 256, 2, 4>(a1, epilogue, rotd, lnf, stats, s);
-            if (rc1 != ESME_OK) return rc1;
-            a2.N = 128;
-            a2.W = a.W + (int64_t)c0 * (a.kt_wrap > 0 ? a.kt_wrap * BK : a.K);
-            if (a.bias) a2.bias = a.bias + c0;
-            if (a.resid) a2.resid = a.resid + c0;
-            a2.C = a.C + c0;
-            if (a.resid32) a2.resid32 = a.resid32 + c0;
-            if (a.ps_in) a2.ps_in = a.ps_in + c0;
-            if (a.ps_out) a2.ps_out = a.ps_out + c0;
-            if (a.col_absmax) a2.col_absmax = a.col_absmax + c0;
-            if (a.stats_out) a2.stats_out = a.stats_out + 2 * (int64_t)(c0 / 256) * a.stat_ld;
-            if (a.ext_off) { a2.ext_base = c0; a2.ext_off = a.ext_off - c0; }
-            return launch_gemm<128, 128, 2, 2>(a2, epilogue, rotd, lnf, stats, s);
-        }
-    }
-    // 256 x 256 tiles run one workgroup per CU, so a launch takes ceil(tiles / CUs) rounds.  (Round 2 measured a "tail split"
-    // -- the last, partly empty round as 128 x 128 tiles in a second launch -- 1 % SLOWER end to end on this power-capped
-    // part; the code is gone.)
-    return launch_gemm<256, 256, 2, 4>(a, epilogue, rotd, lnf, stats, s);      // wave tile 128(m) x 64(n)
+    return launch_gemm<256, 256, 2, 4>(a, f, s);      // wave tile 128(m) x 64(n); one workgroup per CU, so a launch takes ceil(tiles / CUs) rounds
 }
 
 extern "C" int esme_hip_gemm_bf16_fused(const void* A, int64_t lda, const void* W, const void* bias, const void* resid,

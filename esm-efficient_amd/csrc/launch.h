@@ -1,7 +1,7 @@
 // Host-side helpers shared by the C-ABI entry points: argument checks, the thread-local
 // error string behind esme_hip_last_error(), the post-launch error check, and the launch
 // patterns that several entry points share (dynamic-LDS opt-in, LayerNorm-width ladder,
-// grid-z sequence chunks).
+// head-dim and flag ladders, grid-z sequence chunks).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,6 +58,24 @@ inline int dispatch_row_chunks(int64_t E, const char* what, F&& f) {
     if (E <= 5120) return f(std::integral_constant<int, 10>{});
     snprintf(error_buffer(), kErrorBufferSize, "%s: E > 5120 unsupported", what);
     return ESME_ERR_UNSUPPORTED;
+}
+
+// Head-dim ladder of the attention entries: calls f(std::integral_constant<int, D>{}) for the D of the caller's list Ds... that equals d;
+// any other d is refused with `msg`.
+template <int... Ds, class F>
+inline int dispatch_head_dim(int d, const char* msg, F&& f) {
+    int rc = ESME_OK;
+    const bool listed = ((d == Ds && ((rc = f(std::integral_constant<int, Ds>{})), true)) || ...);
+    return listed ? rc : fail(ESME_ERR_UNSUPPORTED, msg);
+}
+
+// Run-time flags to template parameters: calls f(std::bool_constant<b>{}...) for the flags given after it.
+template <class F>
+inline int dispatch_flags(F&& f) { return f(); }
+template <class F, class... B>
+inline int dispatch_flags(F&& f, bool b, B... rest) {
+    return b ? dispatch_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : dispatch_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
 
 // Grid z holds at most `max_z` sequences per launch: calls f(b0, nb) for consecutive chunks of [0, B) and stops at the first
