@@ -18,9 +18,15 @@
 // distinct bank groups).  In the accumulator of one MFMA lane (c = lane & 15, g = lane >> 4) holds rows 4 g + 0..3 of column c.
 // Every index is relative to the sequence's own first row and every reduction has a fixed order: a sequence's map does not
 // depend on its neighbours (bit-identical alone and packed, run to run).  No atomics.
+//
+// The regression's features at chosen residue pairs (include/esme_hip_contact_features.h) run the three statistics kernels
+// unchanged and then
+//  - contact_gather_kernel  per pair (s, i, j) one wave, every head: N_ij = A_ij + A_ji - r_i r_j / t from two fp32 dot products
+//                           and the stored m, l, r, t; D / 8 lanes share a head (16 bytes of each of the four rows per lane).
 #include "common.h"
 #include "launch.h"
 #include "../../include/esme_hip_contacts.h"
+#include "../../include/esme_hip_contact_features.h"
 
 namespace esme {
 
@@ -330,6 +336,95 @@ static int launch_contacts(const ContactArgs& a0, int nt, int64_t npairs, hipStr
     });
 }
 
+// ------------------------------------------------------------------ features at chosen pairs (esme_hip_contact_features.h)
+
+struct GatherArgs {
+    const int32_t* pairs; int64_t P;      // (P, 3) rows (s, i, j); i, j count from the first kept row
+    float* feat; int64_t ld; int col0;    // pair p, head h -> feat[p * ld + col0 + h]
+    int nmax;                             // max_len - f - e: kept rows past it have no statistics
+};
+
+// eight bf16 of one row against eight of another, fp32, elements in index order (bf16 products are exact in fp32)
+__device__ __forceinline__ float dot8(const u32x4 x, const u32x4 y) {
+    float acc = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        acc = fmaf(__uint_as_float(x[w] << 16), __uint_as_float(y[w] << 16), acc);                    // [dot]
+        acc = fmaf(__uint_as_float(x[w] & 0xffff0000u), __uint_as_float(y[w] & 0xffff0000u), acc);    // [dot]
+    }
+    return acc;
+}
+
+// One wave per pair.  D / 8 neighbouring lanes share a head, so a pass covers 512 / D heads; the partial dot products meet in a
+// butterfly over those lanes (every lane of a head ends with the same bits).  q_a . k_b is formed by the same code whichever of
+// the pair's rows a and b are, p1 + p2 and r_i * r_j commute: (i, j) and (j, i) give the same bits.  Nothing depends on the
+// pair's position in the list or on another pair.
+template <int D>
+__global__ __launch_bounds__(256) void contact_gather_kernel(const ContactArgs a, const GatherArgs ga) {
+    constexpr int LPH = D / 8, HPP = 64 / LPH;
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= ga.P) return;                                                  // (wave-uniform)
+    const int s = ga.pairs[3 * p], i = ga.pairs[3 * p + 1], j = ga.pairs[3 * p + 2];
+    float* out = ga.feat + p * ga.ld + ga.col0;
+    bool ok = s >= 0 && s < a.B && i >= 0 && j >= 0;
+    int s0 = 0;
+    if (ok) {                                                               // (cu_lens is read for a sequence of the batch only)
+        s0 = a.cu[s];
+        int n = a.cu[s + 1] - s0 - a.f - a.e;
+        n = n < ga.nmax ? n : ga.nmax;
+        ok = i < n && j < n;
+    }
+    if (!ok) {                                                              // out of range: no q, k or workspace read for it
+        for (int h = lane; h < a.H; h += 64) out[h] = __builtin_nanf("");
+        return;
+    }
+    const int sub = lane % LPH, hl = lane / LPH;
+    const int64_t ri = (int64_t)s0 + a.f + i, rj = (int64_t)s0 + a.f + j;
+    const u16* qi = a.q + ri * a.ld + sub * 8;
+    const u16* ki = a.k + ri * a.ld + sub * 8;
+    const u16* qj = a.q + rj * a.ld + sub * 8;
+    const u16* kj = a.k + rj * a.ld + sub * 8;
+    for (int h0 = 0; h0 < a.H; h0 += HPP) {
+        const bool live = h0 + hl < a.H;
+        const int h = live ? h0 + hl : a.H - 1;                             // idle lanes repeat the last head and store nothing
+        const int c = h * D;
+        float s1 = dot8(*reinterpret_cast<const u32x4*>(qi + c), *reinterpret_cast<const u32x4*>(kj + c));   // q_i . k_j
+        float s2 = dot8(*reinterpret_cast<const u32x4*>(qj + c), *reinterpret_cast<const u32x4*>(ki + c));   // q_j . k_i
+#pragma unroll
+        for (int o = 1; o < LPH; o <<= 1) {
+            s1 += __shfl_xor(s1, o, 64);                                                              // [dot-tree]
+            s2 += __shfl_xor(s2, o, 64);
+        }
+        const int64_t st = (int64_t)h * a.T;
+        const float ii = 1.0f / a.ws_l[st + ri], ij = 1.0f / a.ws_l[st + rj];                         // [inv-l]
+        const float p1 = exp2f(s1 * a.cs - a.ws_m[st + ri]) * ii;                                     // [score-scale] [exp] [normalise]  A_ij
+        const float p2 = exp2f(s2 * a.cs - a.ws_m[st + rj]) * ij;                                     // [score-scale] [exp] [normalise]  A_ji
+        const float it = 1.0f / a.ws_t[(int64_t)h * a.B + s];                                         // [inv-t]
+        const float rr = a.ws_r[st + ri] * a.ws_r[st + rj];                                           // [rr]
+        const float v = fmaf(-rr, it, p1 + p2);                                                       // [sym] [apc]
+        if (live && sub == 0) out[h] = v;
+    }
+}
+
+template <int D>
+static int launch_features(const ContactArgs& a0, const GatherArgs& ga, int nt, hipStream_t s) {
+    if (nt > 0) {
+        const int rc = for_sequence_chunks(a0.B, kContactMaxZ, [&](int b0, int nb) {
+            ContactArgs a = a0;
+            a.b0 = b0;
+            const dim3 tiles((unsigned int)nt, (unsigned int)a.H, (unsigned int)nb);
+            hipLaunchKernelGGL(contact_stats_kernel<D>, tiles, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(contact_colsum_kernel<D>, tiles, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(contact_total_kernel, dim3((unsigned int)a.H, (unsigned int)nb), dim3(64), 0, s, a);
+            return check_launch("contact_features");
+        });
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(contact_gather_kernel<D>, dim3((unsigned int)((ga.P + 3) / 4)), dim3(256), 0, s, a0, ga);
+    return check_launch("contact_features");
+}
+
 }  // namespace esme
 
 using namespace esme;
@@ -369,5 +464,47 @@ extern "C" int esme_hip_contact_layer(const void* q, const void* k, int64_t ld_q
         case 32: return launch_contacts<32>(a, (int)nt, npairs, s);
         case 64: return launch_contacts<64>(a, (int)nt, npairs, s);
         default: return launch_contacts<128>(a, (int)nt, npairs, s);
+    }
+}
+
+extern "C" int64_t esme_hip_contact_features_workspace_bytes(int B, int64_t T, int H) {
+    ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0, "contact_features_workspace_bytes: bad sizes");
+    return (3 * (int64_t)H * T + (int64_t)H * B) * (int64_t)sizeof(float);
+}
+
+extern "C" int esme_hip_contact_features(const void* q, const void* k, int64_t ld_qk, const int32_t* cu_lens, int B, int64_t T, int H,
+                                         int d, int max_len, float softmax_scale, int q_prescaled, int trim_front, int trim_back,
+                                         const int32_t* pairs, int64_t P, float* feat, int64_t ld_feat, int col0, void* workspace,
+                                         int64_t ws_bytes, void* stream) {
+    ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0 && trim_front >= 0 && trim_back >= 0 && P >= 0 && col0 >= 0,
+                   "contact_features: bad sizes");
+    if (B == 0 || T == 0 || P == 0) return ESME_OK;
+    ESME_CHECK_ARG(q && k && cu_lens && pairs && feat && workspace, "contact_features: null pointer");
+    ESME_CHECK_ARG(ld_qk % 8 == 0 && ld_qk >= (int64_t)H * d, "contact_features: bad row stride");
+    ESME_CHECK_ARG(ld_feat >= (int64_t)col0 + H, "contact_features: ld_feat must be at least col0 + H");
+    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(workspace) && (reinterpret_cast<uintptr_t>(feat) & 3u) == 0 &&
+                   (reinterpret_cast<uintptr_t>(pairs) & 3u) == 0, "contact_features: misaligned");
+    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && T < 0x80000000LL && P < 0x80000000LL,
+                   "contact_features: max_len must be > 0, H <= 65535, T < 2^31, P < 2^31");
+    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_features: head dim must be 16, 32, 64 or 128");
+    if ((int64_t)max_len * ld_qk >= ESME_HIP_CONTACT_MAX_SEQ_ELEMS)
+        ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_features: max_len * ld_qk passes 2^32 elements (ESME_HIP_CONTACT_MAX_SEQ_ELEMS)");
+    const int64_t need = esme_hip_contact_features_workspace_bytes(B, T, H);
+    ESME_CHECK_ARG(ws_bytes >= need, "contact_features: workspace too small (see esme_hip_contact_features_workspace_bytes)");
+    int64_t nmax = (int64_t)max_len - trim_front - trim_back;
+    nmax = nmax > 0 ? nmax : 0;                                             // 0: every sequence is trimmed away, every pair out of range
+    const int64_t nt = (nmax + kCT - 1) / kCT;
+    float* ws = (float*)workspace;
+    const int64_t HT = (int64_t)H * T;
+    ContactArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, B, T, H,
+                  q_prescaled ? 1.0f : softmax_scale * 1.4426950408889634f, trim_front, trim_back,
+                  ws, ws + HT, ws + 2 * HT, ws + 3 * HT, nullptr, 0.f, 0, nullptr, nullptr};
+    const GatherArgs ga{pairs, P, feat, ld_feat, col0, (int)nmax};
+    const hipStream_t s = (hipStream_t)stream;
+    switch (d) {
+        case 16: return launch_features<16>(a, ga, (int)nt, s);
+        case 32: return launch_features<32>(a, ga, (int)nt, s);
+        case 64: return launch_features<64>(a, ga, (int)nt, s);
+        default: return launch_features<128>(a, ga, (int)nt, s);
     }
 }

@@ -474,7 +474,8 @@ class ESM2(nn.Module):
     # -- contact prediction (esme/contacts.py) -----------------------------------------
     def set_contact_head(self, head):
         """Install the contact regression: a ContactHead, or anything ContactHead.load accepts (a safetensors / torch file, a state
-        dict).  ValueError unless it has num_layers * attention_heads features.  ESM-C ships no contact regression: supply your own."""
+        dict).  ValueError unless it has num_layers * attention_heads features.  ESM-C and adapted or fine-tuned models ship no contact
+        regression: fit one on proteins of known structure with esme.fit_contact_head(model, batches, contact_maps) (contact_features + ContactHead.fit)."""
         from esme.contacts import ContactHead
         L, H = len(self.layers), self.attention_heads
         if not isinstance(head, ContactHead):
@@ -522,14 +523,41 @@ class ESM2(nn.Module):
                 out[i, :m.shape[0], :m.shape[1]] = m
             return out
 
+    def contact_features(self, tokens, pad_args=None, pairs=None, min_sep=0, lora_names=None, _keep_qk=False):
+        """The contact regression's features at residue pairs: (X, pairs), X float32 (P, num_layers * attention_heads) on the device with
+        X[p, l * H + h] = N^(l,h)_ij (the symmetrised, APC-corrected attention of layer l, head h; esme/contacts.py), pairs int32 (P, 3)
+        rows (s, i, j) with i, j counting the residues of sequence s without bos / eos.  pairs=None: every i < j with j - i >= min_sep
+        of every sequence (min_sep is not applied to a list you pass); else an integer (P, 3) tensor, or a list of one (P_s, 2)
+        tensor of (i, j) rows per sequence -- ValueError on a row out of range.  Needs no contact head: this is what
+        ContactHead.fit is trained on.  Runs the forward in precision 'fast' with one extra kernel call per layer
+        (esme_hip_contact_features); no attention map is stored."""
+        if self.precision != 'fast':
+            raise NotImplementedError(f"contact_features runs in precision 'fast' only; precision {self.precision!r} is not implemented "
+                                      "(set_precision('fast'))")
+        from esme.contacts import ContactFeatureAccumulator, all_pairs, check_pairs
+        box = []
+
+        def make(cu_lens, max_len):
+            n = (cu_lens[1:] - cu_lens[:-1] - 2).clamp(min=0).tolist()          # the alphabets put one bos and one eos around every protein
+            rows = all_pairs(n, min_sep, cu_lens.device) if pairs is None else check_pairs(pairs, n, cu_lens.device)
+            box.append(ContactFeatureAccumulator(rows, cu_lens, max_len, len(self.layers), self.attention_heads, self.head_pad,
+                                                 self.embed_dim // self.attention_heads, trim=(1, 1), keep_qk=_keep_qk))
+            return box[0]
+        with _hip.stream_scope(self.embed_tokens.weight.device):
+            self._forward_representation(tokens, pad_args, False, None, [], lora_names=lora_names, contacts=make)
+            acc = box[0]
+            if _keep_qk:
+                self._contact_qk = acc.qk
+            return acc.result(len(self.layers)), acc.pairs
+
     def graphed(self, tokens, pad_args, what: str = 'forward', clone: bool = True):
         """`getattr(self, what)(tokens, pad_args)` replayed from a hipGraph captured on first use of this
         input shape (esme/graph.py).  For repeated shapes of small batches, where ~160 Python-issued launches
         cost more than the GPU work.  With `clone=False` the result is a static buffer that the next replay of
         the same shape overwrites.  'predict_log_prob' in precision 'half' with half_check = 'sync' checks the token ids, the range flag and the
         plan after each replay, as the eager call does (a widened plan is re-captured and replayed once)."""
-        if what == 'predict_contacts':
-            raise NotImplementedError('graphed(): hipGraph replay of predict_contacts is not implemented; call model.predict_contacts directly')
+        if what in ('predict_contacts', 'contact_features'):
+            raise NotImplementedError(f'graphed(): hipGraph replay of {what} is not implemented; call model.{what} directly')
         assert what in ('forward', 'forward_representation', 'predict_log_prob')
         if self.has_lora:
             raise NotImplementedError('graphed(): hipGraph replay is not implemented for a model with LoRA adapters (a graph bakes one adapter '
