@@ -13,9 +13,7 @@
 //  - contact_pair_kernel    per (sequence, tile pair I <= J), heads in index order: S_IJ = Q_I K_J^T and S_JI^T = K_I Q_J^T land in
 //                           the same register layout, acc += w_h (A_IJ + A_JI^T) - (w_h / t_h) r_I r_J^T; the tile and its mirror
 //                           image are stored (or added to the map) from the same registers: the map is exactly symmetric.
-// A wave owns 16 rows of its tile (fragments straight from global memory, 16 bytes per lane) against the 64 rows of the streamed
-// tile, which the workgroup stages in LDS once (row pitch D + 8 elements: the 16-byte fragment reads of 16 consecutive rows fall on
-// distinct bank groups).  In the accumulator of one MFMA lane (c = lane & 15, g = lane >> 4) holds rows 4 g + 0..3 of column c.
+// The tile code (operand fragments, LDS staging, the score MFMAs) is score_tiles.h, shared with the attention backward.
 // Every index is relative to the sequence's own first row and every reduction has a fixed order: a sequence's map does not
 // depend on its neighbours (bit-identical alone and packed, run to run).  No atomics.
 //
@@ -25,12 +23,12 @@
 //                           and the stored m, l, r, t; D / 8 lanes share a head (16 bytes of each of the four rows per lane).
 #include "common.h"
 #include "launch.h"
+#include "score_tiles.h"
 #include "../../include/esme_hip_contacts.h"
 #include "../../include/esme_hip_contact_features.h"
 
 namespace esme {
 
-static constexpr int kCT = 64;            // tile edge: rows of a workgroup's own tile and of the streamed tile
 static constexpr int kContactMaxZ = 65535;
 
 struct ContactArgs {
@@ -42,65 +40,10 @@ struct ContactArgs {
     const float* w; float bias; int init; float* map; const int64_t* map_off;
 };
 
-template <int D> struct ContactDims {
-    static constexpr int DS = D <= 32 ? 1 : D / 32;     // MFMA k-steps (head dim 16: the upper half of the one step is zero)
-    static constexpr int LD = D + 8;                    // LDS row pitch in elements
-};
-
-__device__ __forceinline__ bf16x8 zero_frag() { return __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u}); }
-
-// operand fragment of row `row`: elements 32 ks + 8 g .. + 7 (A and B operands of the 16x16x32 MFMA share this map)
-template <int D>
-__device__ __forceinline__ bf16x8 global_frag(const u16* base, unsigned int ld, int row, int ks, int g) {
-    if (D == 16 && g >= 2) return zero_frag();
-    return *reinterpret_cast<const bf16x8*>(base + ((unsigned int)row * ld + (unsigned int)(ks * 32 + g * 8)));
-}
-template <int D>
-__device__ __forceinline__ bf16x8 lds_frag(const u16* tile, int row, int ks, int g) {
-    if (D == 16 && g >= 2) return zero_frag();
-    return *reinterpret_cast<const bf16x8*>(tile + row * ContactDims<D>::LD + ks * 32 + g * 8);
-}
-
-// rows row0 .. row0 + 63 of one head's (S, D) operand into LDS; rows past the sequence repeat its last row (their scores are masked)
-template <int D>
-__device__ __forceinline__ void stage_tile(u16* tile, const u16* base, unsigned int ld, int row0, int S) {
-    constexpr int CPR = D / 8, NCH = kCT * CPR;
-    for (int ch = threadIdx.x; ch < NCH; ch += 256) {
-        const int row = ch / CPR, col = (ch % CPR) * 8;
-        int gr = row0 + row;
-        gr = gr < S ? gr : S - 1;
-        *reinterpret_cast<u32x4*>(tile + row * ContactDims<D>::LD + col) =
-            *reinterpret_cast<const u32x4*>(base + ((unsigned int)gr * ld + (unsigned int)col));
-    }
-}
-
-// s[cb][r] = (own row 4 g + r) . (tile row 16 cb + c)
-template <int D>
-__device__ __forceinline__ void score_tile(const bf16x8* a, const u16* tile, int c, int g, f32x4* s) {
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-        s[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < ContactDims<D>::DS; ++ks) s[cb] = mfma_16x16x32<false>(a[ks], lds_frag<D>(tile, cb * 16 + c, ks, g), s[cb]);
-    }
-}
-
-// over the 16 lanes that hold one accumulator row (lane bits 0..3), a fixed butterfly
-__device__ __forceinline__ float row16_max(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void contact_stats_kernel(const ContactArgs a) {
-    constexpr int DS = ContactDims<D>::DS;
-    __shared__ __attribute__((aligned(16))) u16 tile[kCT * ContactDims<D>::LD];
+    constexpr int DS = TileDims<D>::DS;
+    __shared__ __attribute__((aligned(16))) u16 tile[kCT * TileDims<D>::LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
     const int b = a.b0 + blockIdx.z, h = blockIdx.y;
     const int s0 = a.cu[b], S = a.cu[b + 1] - s0, n = S - a.f - a.e;
@@ -172,8 +115,8 @@ __global__ __launch_bounds__(256) void contact_stats_kernel(const ContactArgs a)
 
 template <int D>
 __global__ __launch_bounds__(256) void contact_colsum_kernel(const ContactArgs a) {
-    constexpr int DS = ContactDims<D>::DS;
-    __shared__ __attribute__((aligned(16))) u16 tile[kCT * ContactDims<D>::LD];
+    constexpr int DS = TileDims<D>::DS;
+    __shared__ __attribute__((aligned(16))) u16 tile[kCT * TileDims<D>::LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
     const int b = a.b0 + blockIdx.z, h = blockIdx.y;
     const int s0 = a.cu[b], S = a.cu[b + 1] - s0, n = S - a.f - a.e;
@@ -234,9 +177,9 @@ __global__ __launch_bounds__(64) void contact_total_kernel(const ContactArgs a) 
 
 template <int D>
 __global__ __launch_bounds__(256) void contact_pair_kernel(const ContactArgs a) {
-    constexpr int DS = ContactDims<D>::DS;
-    __shared__ __attribute__((aligned(16))) u16 tk[kCT * ContactDims<D>::LD];
-    __shared__ __attribute__((aligned(16))) u16 tq[kCT * ContactDims<D>::LD];
+    constexpr int DS = TileDims<D>::DS;
+    __shared__ __attribute__((aligned(16))) u16 tk[kCT * TileDims<D>::LD];
+    __shared__ __attribute__((aligned(16))) u16 tq[kCT * TileDims<D>::LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
     const int b = a.b0 + blockIdx.z;
     const int s0 = a.cu[b], S = a.cu[b + 1] - s0, n = S - a.f - a.e;

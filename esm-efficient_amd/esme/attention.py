@@ -561,6 +561,41 @@ class FlashMultiheadAttention(nn.Module):
             return _hip.gemm_fused(a, wo, bo, _hip.EPI_RESIDUAL, alpha=alpha, stats_out=stats_out, **stream)
         return _hip.gemm(a, wo, bo, out=out)
 
+    # -- training (esme/autograd.py): the reference's unfused data flow with a grad_fn ----------------------------------------
+    def check_trainable(self):
+        """NotImplementedError, by name, for what forward_trainable cannot differentiate."""
+        from esme import autograd as ag
+        from esme._hip_attn_bwd import SUPPORTED_HEAD_DIMS
+        from esme.lora import LoRA
+        ag.refuse(self.padded, 'the padded layout (ESM2-35M: head dim 24, a width that is not a multiple of 64) has no backward')
+        ag.refuse(self._q4_qkv is not None or self._q4_out is not None, 'quantised weights have no backward (load the model without quantization=)')
+        ag.refuse(self.head_dim not in SUPPORTED_HEAD_DIMS, f'head dim {self.head_dim}: the attention backward serves head dims {SUPPORTED_HEAD_DIMS}')
+        ag.refuse(self.dropout != 0.0, 'attention dropout > 0 is not implemented')
+        for p in ('q', 'k', 'v', 'out'):
+            m = getattr(self, p)
+            ag.refuse(isinstance(m, LoRA) and m.dropout_p > 0, f'LoRA dropout_p = {getattr(m, "dropout_p", 0)} > 0 is not implemented (dropout is out of scope)')
+            ag.check_linear(m.layer if isinstance(m, LoRA) else m, f'self_attn.{p}')
+
+    def forward_trainable(self, x, cu_lens, max_len, lora_names=None, pos=None):
+        """The attention branch (without the residual) as a differentiable function of x and of the adapters `lora_names` selects
+        (None / empty: all): LayerNorm, q / k / v = frozen projection + adapter deltas (before ESM-C's q / k LayerNorm and before
+        rotary), rotary in torch ops, esme.autograd.VarlenAttention, the out-projection.  The same in train() and eval()."""
+        from esme import autograd as ag
+        self.check_trainable()
+        T = x.shape[0]
+        h = ag.layer_norm(x, self.norm)
+        q, k, v = (ag.lora_linear(h, getattr(self, p), lora_names) for p in ('q', 'k', 'v'))
+        if self.pre_layernorm:
+            q, k = ag.layer_norm(q, self.layernorm_q), ag.layer_norm(k, self.layernorm_k)
+        if self.rot_emb is not None:
+            if pos is None:
+                pos, _ = _hip.seq_positions(cu_lens, T)
+            cos, sin = self.rot_emb.tables(int(max_len), x.device, torch.bfloat16)
+            idx = pos.to(torch.int64)
+            q, k = ag.rotary(q, cos, sin, idx, self.num_heads), ag.rotary(k, cos, sin, idx, self.num_heads)
+        a = ag.VarlenAttention.apply(q, k, v, cu_lens, int(max_len), self.num_heads, self.head_dim ** -0.5)
+        return ag.lora_linear(a, self.out, lora_names)
+
     # -- LoRA adapters (esme/lora.py): the delta rides in an extension K-tile of the projection's own GEMM --------------------
     def _lora_weights(self, lora_names, fold: bool):
         """Derived weights of the adapters `lora_names` selects (None / empty: all), cached on the parameters' version counters and the
@@ -869,6 +904,24 @@ class FlashTransformerLayer(nn.Module):
         _hip.gemm_fused(h, wu, bu, _hip.EPI_GELU if gelu else _hip.EPI_SWIGLU, out=mid, split_a=True, pair_out=True)
         wd, bd = self._weights_down()
         _hip.gemm_fused(mid, wd, bd, _hip.EPI_RESIDUAL, None, alpha, x16, resid32=x32, split_a=True)
+
+    def forward_trainable(self, x, cu_lens, max_len, lora_names=None, pos=None):
+        """x + attn(x) / s, then x + ffn(x) / s (reference attention.py:253-255) with a grad_fn: the attention branch of
+        FlashMultiheadAttention.forward_trainable, the FFN (GELU / SwiGLU) in torch ops around frozen projections."""
+        from esme import autograd as ag
+        ag.refuse(any(q is not None for q in (self._q4_up, self._q4_down)), 'quantised weights have no backward (load the model without quantization=)')
+        x = x + self.self_attn.forward_trainable(x, cu_lens, max_len, lora_names, pos) / self.residue_scaling
+        h = ag.layer_norm(x, self.final[0])
+        if self.final_activation == 'gelu':
+            for lin in (self.final[1], self.final[3]):
+                ag.check_linear(lin, 'the FFN')
+            y = ag.frozen_linear(torch.nn.functional.gelu(ag.frozen_linear(h, self.final[1])), self.final[3])
+        else:
+            sw = self.final[1]
+            for lin in (sw.activation, sw.fc, self.final[2]):
+                ag.check_linear(lin, 'the FFN')
+            y = ag.frozen_linear(torch.nn.functional.silu(ag.frozen_linear(h, sw.activation)) * ag.frozen_linear(h, sw.fc), self.final[2])
+        return x + y / self.residue_scaling
 
     def forward(self, x, cu_lens, max_len, lora_names=None, ctx: Optional[ForwardContext] = None,
                 inplace: bool = False):

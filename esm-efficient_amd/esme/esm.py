@@ -712,6 +712,47 @@ class ESM2(nn.Module):
         self.invalidate_graphs()
         return self
 
+    # -- LoRA fine-tuning (esme/autograd.py) -------------------------------------------------------------------------
+    def forward_trainable(self, tokens, pad_args=None, pad_output=False, pad_indices=None, lora_names=None, logits=True):
+        """model(...) with a grad_fn: logits (T, V) / (B, S, V), or with logits=False the final-LayerNorm representation, as a
+        differentiable function of the adapters `lora_names` selects (None / empty: all) and of the LM head where mark_lmhead(True)
+        made it trainable.  The reference's unfused data flow in bfloat16: the base projections and the attention forward and backward
+        are this package's kernels (esme.autograd.FrozenLinear / VarlenAttention), everything between them torch ops; base weights get
+        no gradient.  The same in train() and eval() (there is no dropout).  `model.train(); model(...)` still raises: the fused
+        inference forward has no backward.  NotImplementedError, by name, for a precision other than 'fast', quantised weights, the
+        padded ESM2-35M layout, dropout > 0, a head dim outside {32, 64} and the learned-position ESM-1 models."""
+        from esme import autograd as ag
+        ag.refuse(self.precision != 'fast', f"precision {self.precision!r} has no backward: training runs in precision 'fast' only")
+        ag.refuse(getattr(self, 'quantization', None) is not None, 'quantised weights have no backward (load the model without quantization=)')
+        ag.refuse(self.padded, 'the padded layout (ESM2-35M: head dim 24, a width that is not a multiple of 64) has no backward')
+        ag.refuse(type(self)._embedding_phys is not ESM2._embedding_phys, 'the learned-position models (ESM-1b / ESM-1v) are not covered')
+        for layer in self.layers:
+            layer.self_attn.check_trainable()
+        if self.has_lora and lora_names:
+            have = self.lora_names()
+            for n in lora_names:
+                if n not in have:
+                    raise KeyError(f'LoRA adapter {n!r} not found (available: {have})')
+        names = tuple(lora_names) if lora_names else None
+        with _hip.stream_scope(self.embed_tokens.weight.device):
+            x = self._embedding_phys(tokens, pad_args)
+            if pad_args is not None:
+                assert tokens.ndim == 1, 'tokens are expected to be unpadded with shape (batch * seq_len)'
+                cu_lens, max_len = pad_args
+            else:
+                assert tokens.ndim == 2, 'tokens are expected to be padded with shape (batch, seq_len, embed_dim)'
+                x, pad_indices, cu_lens, max_len = self._unpad(x, tokens)
+            if cu_lens.dtype != torch.int32:
+                cu_lens = cu_lens.to(torch.int32)
+            max_len = int(max_len)
+            pos, _ = _hip.seq_positions(cu_lens, x.shape[0])
+            for layer in self.layers:
+                x = layer.forward_trainable(x, cu_lens, max_len, names, pos)
+            x = ag.layer_norm(x, self.emb_layer_norm_after)
+            if pad_output or pad_args is None:                    # (before the head, as in forward(): pad rows hold head(0))
+                x = ag.pad_rows(x, pad_indices, cu_lens.numel() - 1, tokens.shape[1] if pad_args is None else max_len)
+            return self.lm_head.forward_trainable(x) if logits else x
+
     def mark_lmhead(self, trainable=True):
         for p in self.lm_head.parameters():
             p.requires_grad_(trainable)

@@ -53,6 +53,16 @@ class RobertaLMHead(nn.Module):
         _hip.gemm_fused(h, fw, self.final.bias, split_a=True, out32=y)
         return y
 
+    def forward_trainable(self, x):
+        """dense -> GELU -> LayerNorm -> vocabulary projection on (..., E) features in torch ops on the head's own parameters (frozen
+        projections of GEMM-tile shape run on the kernel: esme.autograd.frozen_linear), so that mark_lmhead(True) trains it."""
+        from esme import autograd as ag
+        ag.refuse(self.phys_dim != self.embed_dim, 'the padded layout has no backward')
+        shape = x.shape
+        h = torch.nn.functional.gelu(ag.frozen_linear(x.reshape(-1, shape[-1]), self.dense))
+        y = ag.frozen_linear(ag.layer_norm(h, self.layer_norm), self.final)
+        return y.view(*shape[:-1], y.shape[-1])
+
     def forward(self, features):
         shape = features.shape
         x = features.reshape(-1, shape[-1])

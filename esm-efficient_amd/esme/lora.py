@@ -9,8 +9,9 @@ the adapters could no longer be selected per call).  The delta rides in an EXTEN
     [x | u] [W | s B]^T = x W^T + u (s B)^T,        u = x A^T   (esme_hip_lora_down, written next to x in the same buffer)
 
 so it accumulates in fp32 inside the MFMA chain and every fused epilogue of the hot path (LayerNorm fold, rotary, q pre-scale,
-residual, row statistics) is untouched (esme/attention.py).  Inference only: no backward, dropout is stored
-and ignored in eval(), a forward in train() raises.
+residual, row statistics) is untouched (esme/attention.py).  That fused forward is for inference: it has no
+backward, dropout is stored and ignored in eval(), a forward in train() raises.  Adapters are trained through
+`model.forward_trainable` (esme/autograd.py), the reference's unfused data flow with a grad_fn.
 """
 from __future__ import annotations
 

@@ -87,6 +87,22 @@ class Derived:
             yield from flatten_tensors(value)
 
 
+def weight_t(lin) -> torch.Tensor:
+    """W^T (in, out), contiguous, of a projection: the weight operand of dX = dY W on the GEMM kernel (esme.autograd.FrozenLinear).
+    Cached on the projection itself under a name of its own ('wt'), keyed like every derived copy on the weight's address, version
+    counter and the weight-edit epoch: building it leaves the derived weights of the inference paths (which live on the attention
+    block and the layer) in place, and it is rebuilt after the QKV pack moves the weight."""
+    d = lin.__dict__.get('_derived')
+    if d is None:
+        d = lin.__dict__['_derived'] = Derived()
+    w = lin.weight
+    return d.get('wt', (weights_epoch(), w.data_ptr(), w._version), _transposed, w)
+
+
+def _transposed(w):
+    return w.data.t().contiguous()
+
+
 class _TrackedModule(nn.Module):
     def __setattr__(self, name, value):
         if name in ('weight', 'bias'):
