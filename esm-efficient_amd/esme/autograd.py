@@ -1,4 +1,4 @@
-"""The autograd seam of LoRA fine-tuning: the two nodes whose forward AND backward are this package's kernels.
+"""The autograd seam of fine-tuning: the nodes whose forward AND backward are this package's kernels.
 
  - `VarlenAttention`: forward = esme_hip_attn_varlen_fwd on the current stream (the plain form: q not prescaled, bf16), backward =
    esme_hip_attn_varlen_bwd (include/esme_hip_attn_bwd.h).  torch has no stand-in for the backward of block-diagonal attention over a
@@ -6,15 +6,22 @@
  - `FrozenLinear`: a projection whose weight does not require grad: forward = the GEMM kernel, backward dX = dY W on the same kernel
    against W^T from the derived-weight cache (esme.nn.weight_t).  No weight gradient exists for any big GEMM.
 
-`forward_trainable` of the attention block, the layer and the model (esme/attention.py, esme/esm.py) is written with these two and
-torch ops, in the reference's unfused data flow.
+ - `AttentionPooling`: forward = esme_hip_attn_pool on the folded queries U, backward = esme_hip_attn_pool_bwd
+   (include/esme_hip_attn_pool_bwd.h); `pool_fold` is the fold itself in fp32 torch ops, so that autograd carries dU on to the class
+   tokens and the key weight.  `SegmentMean`: forward = esme_hip_segment_mean, backward in torch ops.
+
+`forward_trainable` of the attention block, the layer and the model (esme/attention.py, esme/esm.py) is written with the first two and
+torch ops, in the reference's unfused data flow; `forward_trainable` of the task heads (esme/pooling.py, esme/head.py) with the pooling
+nodes and torch ops.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.nn.functional as F
 
-from esme import _hip, _hip_attn_bwd
+from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd
 from esme.nn import weight_t
 
 
@@ -59,6 +66,78 @@ class FrozenLinear(torch.autograd.Function):
         if dy.stride(1) != 1 or dy.stride(0) % 8 or dy.data_ptr() % 16:
             dy = dy.contiguous()
         return _hip.gemm(dy, ctx.wt), None, None, None
+
+
+class AttentionPooling(torch.autograd.Function):
+    """out (B, n_cls, E) = attention pooling of embed (T, E) bfloat16 / float32 with the folded queries U (n_cls * heads, E) float32
+    (`pool_fold`); differentiable in embed and U."""
+
+    @staticmethod
+    def forward(ctx, embed, cu_lens, U, heads, n_cls):
+        if cu_lens.dtype != torch.int32:
+            cu_lens = cu_lens.to(torch.int32)
+        embed, U = embed.detach(), U.detach().contiguous()
+        if embed.stride(-1) != 1:
+            embed = embed.contiguous()
+        ctx.save_for_backward(embed, U, cu_lens)
+        ctx.args = (int(heads), int(n_cls))
+        return _hip.attn_pool(embed, cu_lens, U, int(heads), int(n_cls))
+
+    @staticmethod
+    def backward(ctx, d_out):
+        embed, U, cu_lens = ctx.saved_tensors
+        heads, n_cls = ctx.args
+        dx, dU = _hip_attn_pool_bwd.attn_pool_bwd(embed, cu_lens, U, d_out.contiguous(), heads, n_cls, need_dx=ctx.needs_input_grad[0])
+        return dx, None, (dU if ctx.needs_input_grad[2] else None), None, None
+
+
+def pool_fold(cls: torch.Tensor, k_weight: torch.Tensor, heads: int) -> torch.Tensor:
+    """U (n_cls * heads, E) float32 = log2(e) / sqrt(d) * W_k[h d:(h+1) d, :]^T cls[c, h d:(h+1) d] in fp32 torch ops: what
+    esme_hip_attn_pool_fold computes (to fp32 rounding), differentiable in cls and k_weight."""
+    C, E = cls.shape
+    d = E // heads
+    scale = 1.4426950408889634 / math.sqrt(d)                       # (rounded to fp32 by the product, as the kernel's)
+    u = torch.einsum('chd,hde->che', cls.float().view(C, heads, d), k_weight.float().view(heads, d, E))
+    return (u * scale).reshape(C * heads, E)
+
+
+class SegmentMean(torch.autograd.Function):
+    """(B, E) per-sequence mean of the rows of x (T, E) bfloat16 / float32 (esme_hip_segment_mean); backward dY[seg] / len in torch
+    ops, in x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, cu_lens):
+        if cu_lens.dtype != torch.int32:
+            cu_lens = cu_lens.to(torch.int32)
+        ctx.save_for_backward(cu_lens)
+        ctx.rows = x.shape[0]
+        x = x.detach()
+        return _hip.segment_mean(x if x.stride(-1) == 1 else x.contiguous(), cu_lens)
+
+    @staticmethod
+    def backward(ctx, dy):
+        cu_lens, = ctx.saved_tensors
+        lens = (cu_lens[1:] - cu_lens[:-1]).to(torch.long)
+        g = (dy.float() / lens.clamp(min=1).view(-1, 1)).to(dy.dtype)
+        dx = torch.zeros(ctx.rows, dy.shape[1], dtype=dy.dtype, device=dy.device)
+        seg = torch.repeat_interleave(torch.arange(lens.numel(), device=dy.device), lens)
+        start = int(cu_lens[0])
+        dx[start:start + seg.numel()] = g[seg]
+        return dx, None
+
+
+def relu_mlp(x: torch.Tensor, lin, final) -> torch.Tensor:
+    """final(relu(lin(x))) in torch ops on the modules' own parameters: the part of a task head that is trained."""
+    w = (lambda p: p) if x.dtype == torch.bfloat16 else (lambda p: p.to(x.dtype))     # (a float32 embedding: the bf16 values in fp32 ops)
+    return F.linear(F.relu(F.linear(x, w(lin.weight), w(lin.bias))), w(final.weight), w(final.bias))
+
+
+def check_head_input(x: torch.Tensor, params, what: str) -> None:
+    """What the task heads' forward_trainable serves: bfloat16 parameters and a bfloat16 or float32 embedding on a HIP device."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'{what}: embed must be bfloat16 or float32, got {x.dtype}')
+    for n, p in params:
+        refuse(p.dtype != torch.bfloat16, f'{what}: parameter {n} is {p.dtype}; the heads keep bfloat16 parameters')
 
 
 def frozen_linear(x: torch.Tensor, lin) -> torch.Tensor:

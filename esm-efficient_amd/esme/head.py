@@ -4,7 +4,7 @@ and the mean-pooling classification head `ClsHead` (esme/head.py:30-68).
 The exact-erf GELU is the dense GEMM's epilogue; the vocab projection (N = 33 / 64,
 HBM-bound) runs on the same GEMM kernel with row-clamped weight loads.  ClsHead pools
 with esme_hip_segment_mean, runs its first Linear on the GEMM and the ReLU + last Linear
-in esme_hip_relu_linear (inference only)."""
+in esme_hip_relu_linear (`forward`: inference only; `forward_trainable`: the same function with a backward)."""
 from __future__ import annotations
 
 import torch
@@ -105,3 +105,13 @@ class ClsHead(nn.Module):
             raise TypeError(f'ClsHead: x must be bfloat16 or float32, got {x.dtype}')
         pooled = self.pool(x, cu_lens)
         return self._mlp(pooled, self.head[0], self.head[2]).squeeze(-1)
+
+    def forward_trainable(self, x, cu_lens):
+        """`forward` with a backward: the same arguments, output shape and dtype, in train() and eval() alike.  The mean pool is the
+        kernel (esme.autograd.SegmentMean; its backward spreads dY / length over the sequence's rows, for an x that requires grad), the
+        MLP is torch ops (F.linear, relu) on the head's own bfloat16 parameters, which are what is trained.  Parameters are created with
+        requires_grad=False; opt in with `head.requires_grad_(True)`."""
+        from esme import autograd as ag
+        ag.check_head_input(x, [(n, p) for n, p in self.named_parameters()], 'ClsHead')
+        pooled = ag.SegmentMean.apply(x, cu_lens)
+        return ag.relu_mlp(pooled, self.head[0], self.head[2]).squeeze(-1)

@@ -9,8 +9,9 @@ and accumulated in fp32 -- the reference accumulates in the embedding dtype with
 
 The attention-pooling heads keep the reference's names, arguments and state-dict keys
 (`AttentionPool`, `LearnedAttentionPool`, `LearnedAggregation`, `BinaryLearnedAggregation`,
-esme/pooling.py:72-228), for inference only: parameters have requires_grad=False and
-`dropout_p` must be 0.  The reference projects every residue with `k` and runs flash
+esme/pooling.py:72-228).  `forward` is inference only: it detaches its inputs; parameters are
+created with requires_grad=False and `dropout_p` must be 0.  `forward_trainable` is the same
+function with a backward (opt in with `head.requires_grad_(True)`; see AttentionPool.forward_trainable).  The reference projects every residue with `k` and runs flash
 attention on n_cls repeated copies; here the projection is folded into the class-token
 queries (`esme_hip_attn_pool_fold`, recomputed on every call) and one kernel reads the
 embedding once (`esme_hip_attn_pool`).  Because the queries are fixed, `k.bias` adds a
@@ -127,6 +128,24 @@ class AttentionPool(nn.Module):
         return _hip.attn_pool(embed, cu_lens, U, self.attention_heads, q.shape[0])
 
 
+    def forward_trainable(self, cls: torch.Tensor, embed: torch.Tensor, pad_args: Tuple[torch.Tensor, int]) -> torch.Tensor:
+        """`forward` with a backward: the same arguments, output shape and dtype, in train() and eval() alike.  Differentiable in
+        `cls`, `k.weight` and `embed` (bfloat16 or float32), each where it requires grad: the pooling and its backward are the HIP
+        kernels (esme.autograd.AttentionPooling), the fold of `k` into `cls` is fp32 torch ops.  Parameters are created with
+        requires_grad=False; a user opts in with `head.requires_grad_(True)`.  `k.bias` adds a constant to every score of a (class
+        token, head) and cancels in the softmax: its gradient is zero and it is given none (`k.bias.grad is None`).  Embeddings the
+        embedding gradient is not wanted for (a frozen backbone: `forward_representation` under no_grad) skip that part of the
+        backward kernel.  Parameters must be bfloat16 (NotImplementedError otherwise)."""
+        from esme import autograd as ag
+        cu_lens, _max_len = pad_args
+        _check_embed(embed, self.embed_dim)
+        if cls.dim() != 2 or cls.shape[1] != self.embed_dim:
+            raise ValueError(f'attention pooling: cls must be (n_cls, {self.embed_dim}), got {tuple(cls.shape)}')
+        ag.check_head_input(embed, [('cls', cls), ('k.weight', self.k.weight)], 'attention pooling')
+        U = ag.pool_fold(cls, self.k.weight, self.attention_heads)
+        return ag.AttentionPooling.apply(embed, cu_lens, U, self.attention_heads, cls.shape[0])
+
+
 class LearnedAttentionPool(AttentionPool):
     """AttentionPool with `num_cls` learned class tokens, key `cls` (ones at construction, as the reference:
     esme/pooling.py:139-181).  `forward(embed, pad_args)` -> (n_seq, num_cls, E)."""
@@ -137,6 +156,10 @@ class LearnedAttentionPool(AttentionPool):
 
     def forward(self, embed: torch.Tensor, pad_args: Tuple[torch.Tensor, int]) -> torch.Tensor:
         return super().forward(self.cls, embed, pad_args)
+
+    def forward_trainable(self, embed: torch.Tensor, pad_args: Tuple[torch.Tensor, int]) -> torch.Tensor:
+        """`forward` with a backward (AttentionPool.forward_trainable) on the learned class tokens."""
+        return super().forward_trainable(self.cls, embed, pad_args)
 
 
 class LearnedAggregation(nn.Module):
@@ -157,6 +180,15 @@ class LearnedAggregation(nn.Module):
         y = self._mlp(x.reshape(n * c, E), self.linear, self.final)
         return y.view(n, c, 1).squeeze(1)
 
+    def forward_trainable(self, embed: torch.Tensor, pad_args: Tuple[torch.Tensor, int]) -> torch.Tensor:
+        """`forward` with a backward: the pooling as AttentionPool.forward_trainable, the MLP after it in torch ops (F.linear, relu) on
+        `linear` and `final`, the weights being trained.  The same output shape and dtype as `forward`, in train() and eval() alike;
+        opt in with `head.requires_grad_(True)`; `attn.k.bias` gets no gradient (it is zero)."""
+        from esme import autograd as ag
+        ag.check_head_input(embed, [(n, p) for n, p in self.named_parameters()], 'LearnedAggregation')
+        x = self.attn.forward_trainable(embed, pad_args)
+        return ag.relu_mlp(x, self.linear, self.final).squeeze(1)
+
 
 class BinaryLearnedAggregation(LearnedAggregation):
     """LearnedAggregation with one class token, squeezed to (n_seq,) (reference esme/pooling.py:222-228)."""
@@ -166,3 +198,7 @@ class BinaryLearnedAggregation(LearnedAggregation):
 
     def forward(self, embed: torch.Tensor, pad_args: Tuple[torch.Tensor, int]) -> torch.Tensor:
         return super().forward(embed, pad_args).squeeze(-1)
+
+    def forward_trainable(self, embed: torch.Tensor, pad_args: Tuple[torch.Tensor, int]) -> torch.Tensor:
+        """`forward` with a backward (LearnedAggregation.forward_trainable), squeezed to (n_seq,)."""
+        return super().forward_trainable(embed, pad_args).squeeze(-1)
