@@ -915,12 +915,12 @@ class FlashTransformerLayer(nn.Module):
         if self.final_activation == 'gelu':
             for lin in (self.final[1], self.final[3]):
                 ag.check_linear(lin, 'the FFN')
-            y = ag.frozen_linear(torch.nn.functional.gelu(ag.frozen_linear(h, self.final[1])), self.final[3])
+            y = ag.frozen_linear(torch.nn.functional.gelu(ag.frozen_linear(h, self.final[1], True)), self.final[3], True)
         else:
             sw = self.final[1]
             for lin in (sw.activation, sw.fc, self.final[2]):
                 ag.check_linear(lin, 'the FFN')
-            y = ag.frozen_linear(torch.nn.functional.silu(ag.frozen_linear(h, sw.activation)) * ag.frozen_linear(h, sw.fc), self.final[2])
+            y = ag.frozen_linear(torch.nn.functional.silu(ag.frozen_linear(h, sw.activation, True)) * ag.frozen_linear(h, sw.fc, True), self.final[2], True)
         return x + y / self.residue_scaling
 
     def forward(self, x, cu_lens, max_len, lora_names=None, ctx: Optional[ForwardContext] = None,

@@ -4,7 +4,9 @@
    esme_hip_attn_varlen_bwd (include/esme_hip_attn_bwd.h).  torch has no stand-in for the backward of block-diagonal attention over a
    cu_lens-packed batch; everything else of a training step is torch.autograd on torch ops.
  - `FrozenLinear`: a projection whose weight does not require grad: forward = the GEMM kernel, backward dX = dY W on the same kernel
-   against W^T from the derived-weight cache (esme.nn.weight_t).  No weight gradient exists for any big GEMM.
+   against W^T from the derived-weight cache (esme.nn.weight_t).
+ - `TrainableLinear`: a layer's own projection whose weight requires grad (model.mark_trainable): the same forward and dX, and
+   (dW, db) = esme_hip_gemm_wgrad (include/esme_hip_gemm_wgrad.h) in bfloat16, the parameters' dtype.
 
  - `AttentionPooling`: forward = esme_hip_attn_pool on the folded queries U, backward = esme_hip_attn_pool_bwd
    (include/esme_hip_attn_pool_bwd.h); `pool_fold` is the fold itself in fp32 torch ops, so that autograd carries dU on to the class
@@ -21,7 +23,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd
+from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_gemm_wgrad
 from esme.nn import weight_t
 
 
@@ -66,6 +68,37 @@ class FrozenLinear(torch.autograd.Function):
         if dy.stride(1) != 1 or dy.stride(0) % 8 or dy.data_ptr() % 16:
             dy = dy.contiguous()
         return _hip.gemm(dy, ctx.wt), None, None, None
+
+
+def _kernel_rows(t: torch.Tensor) -> torch.Tensor:
+    """t as the GEMM kernels read a 2-D operand: unit column stride, a row stride that is a multiple of 8, a 16-byte aligned base."""
+    if t.stride(1) != 1 or t.stride(0) % 8 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+class TrainableLinear(torch.autograd.Function):
+    """y = x W^T + b on the GEMM kernel for a projection `lin` that is trained: dX = dY W on the same kernel (W^T from
+    esme.nn.weight_t, whose key holds the weight's version counter: it is rebuilt after an optimiser step), dW = dY^T X and
+    db = the column sums of dY on esme_hip_gemm_wgrad, in bfloat16."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, lin):
+        x = _kernel_rows(x.detach())
+        ctx.save_for_backward(x, w)
+        ctx.lin, ctx.has_bias = lin, b is not None
+        return _hip.gemm(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, _ = ctx.saved_tensors
+        dy = _kernel_rows(dy)
+        dx = _hip.gemm(dy, weight_t(ctx.lin)) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_b:
+            dw, db = _hip_gemm_wgrad.gemm_wgrad(dy, x, bias=want_b)
+        return dx, (dw if ctx.needs_input_grad[1] else None), db, None
 
 
 class AttentionPooling(torch.autograd.Function):
@@ -140,14 +173,18 @@ def check_head_input(x: torch.Tensor, params, what: str) -> None:
         refuse(p.dtype != torch.bfloat16, f'{what}: parameter {n} is {p.dtype}; the heads keep bfloat16 parameters')
 
 
-def frozen_linear(x: torch.Tensor, lin) -> torch.Tensor:
-    """lin(x) for a 2-D bfloat16 x, differentiable in x (and in lin's parameters where they require grad).  The kernels serve a frozen
-    bfloat16 projection whose two widths are multiples of the GEMM's K tile of 64; a trainable one (mark_lmhead) or another shape (the
-    vocabulary projection: dX = dY W has K = vocab_size) is torch's F.linear."""
+def frozen_linear(x: torch.Tensor, lin, layer_projection: bool = False) -> torch.Tensor:
+    """lin(x) for a 2-D bfloat16 x, differentiable in x (and in lin's parameters where they require grad).  The kernels serve a
+    bfloat16 projection whose two widths are multiples of 64 (the GEMM's K tile, the weight-gradient kernel's wave tile): frozen, it is
+    `FrozenLinear`; trained (model.mark_trainable) and one of a layer's own projections (`layer_projection`: q, k, v, out, FFN up /
+    down, SwiGLU's two), it is `TrainableLinear`.  Any other trainable projection (the LM head after mark_lmhead) and any other shape
+    (the vocabulary projection: dX = dY W has K = vocab_size) is torch's F.linear."""
     w, b = lin.weight, lin.bias
     trainable = w.requires_grad or (b is not None and b.requires_grad)
-    if trainable or w.shape[0] % 64 or w.shape[1] % 64:
+    if w.shape[0] % 64 or w.shape[1] % 64 or (trainable and not layer_projection):
         return F.linear(x, w, b)
+    if trainable:
+        return TrainableLinear.apply(x, w, b, lin)
     return FrozenLinear.apply(x, w, b, weight_t(lin))
 
 
@@ -156,8 +193,8 @@ def lora_linear(x: torch.Tensor, mod, names) -> torch.Tensor:
     base(x) + sum_n scaling * (x A_n^T) B_n^T, the delta in torch ops (the gradients of A_n and B_n are torch's)."""
     from esme.lora import LoRA
     if not isinstance(mod, LoRA):
-        return frozen_linear(x, mod)
-    y = frozen_linear(x, mod.layer)
+        return frozen_linear(x, mod, True)
+    y = frozen_linear(x, mod.layer, True)
     for n in mod.select(names):
         y = y + F.linear(F.linear(x, mod.lora_A[n]), mod.lora_B[n]) * mod.scaling
     return y

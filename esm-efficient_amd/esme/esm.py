@@ -14,8 +14,10 @@ ESM-1b / ESM-1v (learned positions, no rotary) run on the same kernels (`ESM1b`,
 LoRA adapters (`add_lora` / `load_lora` / `save_lora`, `lora_names=`) run for inference in precision 'fast' (esme/lora.py).
 `predict_contacts` (with `set_contact_head`) reduces the attention maps into contact maps layer by layer (esme/contacts.py); the
 reference has no counterpart (flash-attn returns no attention weights).
-Out of scope here: training (no backward), int8-activation matmuls,
-activation checkpointing (training only), hub download (no network).
+Training goes through `forward_trainable` (esme/autograd.py): LoRA adapters, the LM head (`mark_lmhead`) and, after `mark_trainable`,
+the layers' own projections and LayerNorms (full fine-tuning; `checkpoint_layers=True` is the reference's `checkpointing=`).
+Out of scope here: a backward of the fused inference forward (`model.train(); model(...)` raises, and the
+constructor's `checkpointing=` with it), int8-activation matmuls, hub download (no network).
 """
 from __future__ import annotations
 
@@ -713,15 +715,22 @@ class ESM2(nn.Module):
         return self
 
     # -- LoRA fine-tuning (esme/autograd.py) -------------------------------------------------------------------------
-    def forward_trainable(self, tokens, pad_args=None, pad_output=False, pad_indices=None, lora_names=None, logits=True):
+    def forward_trainable(self, tokens, pad_args=None, pad_output=False, pad_indices=None, lora_names=None, logits=True,
+                          checkpoint_layers=False):
         """model(...) with a grad_fn: logits (T, V) / (B, S, V), or with logits=False the final-LayerNorm representation, as a
-        differentiable function of the adapters `lora_names` selects (None / empty: all) and of the LM head where mark_lmhead(True)
-        made it trainable.  The reference's unfused data flow in bfloat16: the base projections and the attention forward and backward
-        are this package's kernels (esme.autograd.FrozenLinear / VarlenAttention), everything between them torch ops; base weights get
-        no gradient.  The same in train() and eval() (there is no dropout).  `model.train(); model(...)` still raises: the fused
-        inference forward has no backward.  NotImplementedError, by name, for a precision other than 'fast', quantised weights, the
-        padded ESM2-35M layout, dropout > 0, a head dim outside {32, 64} and the learned-position ESM-1 models."""
+        differentiable function of the adapters `lora_names` selects (None / empty: all), of the LM head where mark_lmhead(True)
+        made it trainable, and of the layers' projections and LayerNorms where mark_trainable() did (full fine-tuning).  The
+        reference's unfused data flow in bfloat16: the base projections (forward, dX and, where trained, dW / db) and the attention
+        forward and backward are this package's kernels (esme.autograd.FrozenLinear / TrainableLinear / VarlenAttention), everything
+        between them torch ops.  `checkpoint_layers=True` runs every layer under torch.utils.checkpoint (non-reentrant): only the
+        layers' inputs are kept and each layer is recomputed in the backward -- the reference's `checkpointing=`; every kernel on the
+        path is deterministic, so loss and gradients are bit-equal with and without it.  The same in train() and eval() (there is no
+        dropout).  `model.train(); model(...)` still raises: the fused inference forward has no backward.  NotImplementedError, by
+        name, for a precision other than 'fast', quantised weights, the padded ESM2-35M layout, dropout > 0, a head dim outside
+        {32, 64}, the learned-position ESM-1 models and a token embedding that requires grad (its kernel has no backward)."""
         from esme import autograd as ag
+        ag.refuse(self.embed_tokens.weight.requires_grad, 'embed_tokens.weight requires grad, but the token embedding has no backward: '
+                  'select what to train with model.mark_trainable() (projections and LayerNorms), which leaves the embedding frozen')
         ag.refuse(self.precision != 'fast', f"precision {self.precision!r} has no backward: training runs in precision 'fast' only")
         ag.refuse(getattr(self, 'quantization', None) is not None, 'quantised weights have no backward (load the model without quantization=)')
         ag.refuse(self.padded, 'the padded layout (ESM2-35M: head dim 24, a width that is not a multiple of 64) has no backward')
@@ -747,7 +756,11 @@ class ESM2(nn.Module):
             max_len = int(max_len)
             pos, _ = _hip.seq_positions(cu_lens, x.shape[0])
             for layer in self.layers:
-                x = layer.forward_trainable(x, cu_lens, max_len, names, pos)
+                if checkpoint_layers:
+                    from torch.utils.checkpoint import checkpoint
+                    x = checkpoint(layer.forward_trainable, x, cu_lens, max_len, names, pos, use_reentrant=False)
+                else:
+                    x = layer.forward_trainable(x, cu_lens, max_len, names, pos)
             x = ag.layer_norm(x, self.emb_layer_norm_after)
             if pad_output or pad_args is None:                    # (before the head, as in forward(): pad rows hold head(0))
                 x = ag.pad_rows(x, pad_indices, cu_lens.numel() - 1, tokens.shape[1] if pad_args is None else max_len)
@@ -756,6 +769,49 @@ class ESM2(nn.Module):
     def mark_lmhead(self, trainable=True):
         for p in self.lm_head.parameters():
             p.requires_grad_(trainable)
+        return self
+
+    # -- full fine-tuning (esme/autograd.py TrainableLinear, include/esme_hip_gemm_wgrad.h) --------------------------------------
+    def mark_trainable(self, projections=True, norms=True, layers=None):
+        """Select what full fine-tuning trains through `forward_trainable`.  `projections`: requires_grad on the weights and biases of
+        the selected layers' own projections (q, k, v, out, FFN up / down, SwiGLU's two; under a LoRA wrapper the base `layer`) --
+        their gradients come from esme_hip_gemm_wgrad.  `norms`: on the selected layers' LayerNorms (ESM-C's q / k norms included) and,
+        when `layers` is None, on `emb_layer_norm_after`, which belongs to no layer -- their gradients are torch's.  `layers`: indices
+        (negative ones count from the end) for the "unfreeze the top k layers" recipe; None: all.  Every layer that is not selected
+        is frozen, so `mark_trainable(False, False)` freezes the backbone again.  The token embedding stays frozen (its kernel has no
+        backward), and the LM head and LoRA adapters keep their flags (mark_lmhead, mark_only_lora_as_trainable)."""
+        from esme.lora import LoRA
+        L = len(self.layers)
+        if layers is None:
+            chosen = set(range(L))
+        else:
+            chosen = set()
+            for i in layers:
+                if not -L <= int(i) < L:
+                    raise IndexError(f'mark_trainable: layer {i} of a model with {L} layers')
+                chosen.add(int(i) % L)
+        for i, layer in enumerate(self.layers):
+            att = layer.self_attn
+            lins = [getattr(att, p) for p in ('q', 'k', 'v', 'out')]
+            if layer.final_activation == 'gelu':
+                lins += [layer.final[1], layer.final[3]]
+            else:
+                lins += [layer.final[1].activation, layer.final[1].fc, layer.final[2]]
+            lns = [att.norm, layer.final[0]] + ([att.layernorm_q, att.layernorm_k] if att.pre_layernorm else [])
+            for lin in lins:
+                lin = lin.layer if isinstance(lin, LoRA) else lin
+                want = bool(projections) and i in chosen
+                if want and not lin.weight.dtype.is_floating_point:
+                    raise NotImplementedError(f'mark_trainable: layer {i} is stored quantised ({lin.weight.dtype}); training needs '
+                                              'unquantised bfloat16 base weights')
+                for p in (lin.weight, lin.bias):
+                    if p is not None and (want or p.requires_grad):
+                        p.requires_grad_(want)
+            for ln in lns:
+                for p in ln.parameters(recurse=False):
+                    p.requires_grad_(bool(norms) and i in chosen)
+        for p in self.emb_layer_norm_after.parameters(recurse=False):
+            p.requires_grad_(bool(norms) and layers is None)
         return self
 
     # -- loading -------------------------------------------------------------------
