@@ -13,7 +13,8 @@ that is not on a HIP device raises (there is no CPU fallback).
 ESM-1b / ESM-1v (learned positions, no rotary) run on the same kernels (`ESM1b`, `ESM1v`).
 LoRA adapters (`add_lora` / `load_lora` / `save_lora`, `lora_names=`) run for inference in precision 'fast' (esme/lora.py).
 `predict_contacts` (with `set_contact_head`) reduces the attention maps into contact maps layer by layer (esme/contacts.py); the
-reference has no counterpart (flash-attn returns no attention weights).
+reference has no counterpart (flash-attn returns no attention weights).  `attention_maps` writes the maps of chosen layers and
+heads themselves out (esme/attention_maps.py).
 Training goes through `forward_trainable` (esme/autograd.py): LoRA adapters, the LM head (`mark_lmhead`) and, after `mark_trainable`,
 the layers' own projections and LayerNorms (full fine-tuning; `checkpoint_layers=True` is the reference's `checkpointing=`).
 Out of scope here: a backward of the fused inference forward (`model.train(); model(...)` raises, and the
@@ -552,13 +553,67 @@ class ESM2(nn.Module):
                 self._contact_qk = acc.qk
             return acc.result(len(self.layers)), acc.pairs
 
+    # -- attention maps (esme/attention_maps.py) -----------------------------------------
+    def attention_maps(self, tokens, pad_args=None, pad_output=False, layers=None, heads=None, head_weights=None,
+                       dtype=torch.float32, lora_names=None, max_bytes=4 << 30, _keep_qk=False):
+        """Attention weights softmax(q k^T * scale) of chosen layers and heads, bos / eos rows and columns included (what fair-esm's
+        need_head_weights=True and Hugging Face's output_attentions=True return).  `layers` / `heads`: index lists (negative indices count
+        from the end, None = all; IndexError out of range, ValueError on duplicates).  `head_weights`: None, 'mean' (1 / number of
+        selected heads) or a float tensor (len(layers), len(heads)): the selected heads of each layer are summed with these weights into
+        ONE map per layer.  `dtype`: torch.float32 or torch.bfloat16.  Packed input (`pad_args=(cu_lens, max_len)`): a list of B views
+        of one buffer, each (L_sel, H_sel, S_b, S_b) -- with head_weights (L_sel, S_b, S_b); 2-D tokens or `pad_output=True`: a dense
+        (B, L_sel, H_sel, S, S) / (B, L_sel, S, S) tensor, zero outside each protein's block.  The buffer takes
+        L_sel * n_out * sum_b S_b^2 * itemsize bytes (n_out = H_sel, or 1 with head_weights): ValueError before the forward runs when
+        that exceeds `max_bytes`.  Runs the forward in precision 'fast' with one extra kernel call per SELECTED layer
+        (esme_hip_attn_maps)."""
+        if self.precision != 'fast':
+            raise NotImplementedError(f"attention_maps runs in precision 'fast' only; precision {self.precision!r} is not implemented "
+                                      "(set_precision('fast'))")
+        from esme import attention_maps as AM
+        if dtype not in AM.DTYPES:
+            raise ValueError(f'attention_maps: dtype must be torch.float32 or torch.bfloat16, got {dtype}')
+        lsel = AM.select_indices(layers, len(self.layers), 'layers')
+        hsel = AM.select_indices(heads, self.attention_heads, 'heads')
+        weights = AM.check_head_weights(head_weights, len(lsel), len(hsel))
+        n_out = 1 if weights is not None else len(hsel)
+        if pad_args is not None:
+            lengths = (pad_args[0][1:] - pad_args[0][:-1]).tolist()
+        else:
+            lengths = tokens.ne(self.alphabet.padding_idx).sum(dim=1).tolist()
+        need = AM.buffer_bytes(lengths, len(lsel), n_out, dtype)
+        if need > max_bytes:
+            raise ValueError(f'attention_maps: the maps need {need} bytes (L_sel * n_out * sum_b S_b^2 * itemsize = {len(lsel)} * {n_out} * '
+                             f'{sum(s * s for s in lengths)} * {2 if dtype == torch.bfloat16 else 4}), more than '
+                             f'max_bytes = {max_bytes}: select fewer layers= or heads=, pass head_weights= (one map per layer), use '
+                             'dtype=torch.bfloat16, send fewer or shorter proteins per call, or raise max_bytes=')
+        box = []
+
+        def make(cu_lens, max_len):
+            box.append(AM.AttentionMapAccumulator(lsel, hsel, weights, dtype, cu_lens, max_len, self.attention_heads, self.head_pad,
+                                                  self.embed_dim // self.attention_heads, keep_qk=_keep_qk))
+            return box[0]
+        with _hip.stream_scope(self.embed_tokens.weight.device):
+            self._forward_representation(tokens, pad_args, False, None, [], lora_names=lora_names, contacts=make)
+            acc = box[0]
+            maps = acc.result()
+            if _keep_qk:
+                self._contact_qk = acc.qk
+            if not (pad_output or pad_args is None):
+                return maps
+            width = tokens.shape[1] if pad_args is None else acc.max_len
+            lead = (len(lsel),) if weights is not None else (len(lsel), n_out)
+            out = torch.zeros(len(maps), *lead, width, width, dtype=dtype, device=acc.out.device)
+            for i, m in enumerate(maps):
+                out[i, ..., :m.shape[-2], :m.shape[-1]] = m
+            return out
+
     def graphed(self, tokens, pad_args, what: str = 'forward', clone: bool = True):
         """`getattr(self, what)(tokens, pad_args)` replayed from a hipGraph captured on first use of this
         input shape (esme/graph.py).  For repeated shapes of small batches, where ~160 Python-issued launches
         cost more than the GPU work.  With `clone=False` the result is a static buffer that the next replay of
         the same shape overwrites.  'predict_log_prob' in precision 'half' with half_check = 'sync' checks the token ids, the range flag and the
         plan after each replay, as the eager call does (a widened plan is re-captured and replayed once)."""
-        if what in ('predict_contacts', 'contact_features'):
+        if what in ('predict_contacts', 'contact_features', 'attention_maps'):
             raise NotImplementedError(f'graphed(): hipGraph replay of {what} is not implemented; call model.{what} directly')
         assert what in ('forward', 'forward_representation', 'predict_log_prob')
         if self.has_lora:
