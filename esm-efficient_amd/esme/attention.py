@@ -25,7 +25,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -212,6 +212,13 @@ class HalfPlan:
         return f"ext channels {0 if self.ext_sel is None else self.ext_sel.numel()}, q/k pairs {'on' if self.qk_pair else 'off'}{where}" + (', fixed-reference attention' if self.qp else '')
 
 
+class ExtBlock(NamedTuple):
+    """The extension columns [s B | 0] of a LoRA-extended weight on their own (`block`: (rows, X) bf16): what _lora_weights caches over a
+    quantised base, where the base columns are expanded from the codes per call (FlashMultiheadAttention._lora_extended).  (A tuple, so
+    that Derived.tensors() finds the block.)"""
+    block: torch.Tensor
+
+
 def has_pair_form(att) -> bool:
     """The block of attention module `att` has a q/k-pair form (HalfPlan.qk_pair): no q/k LayerNorm, head dim <= 64, width a multiple of 128."""
     return (not att.pre_layernorm) and att.head_pad in (16, 32, 64) and att.attn_dim % 128 == 0
@@ -358,6 +365,7 @@ class FlashMultiheadAttention(nn.Module):
         self._q4_qkv = None         # esme.quantization.Q4Matrix pair when the layer is 4-bit
         self._q4_out = None
         self._has_lora = False      # set by ESM2.add_lora: q / k / v / out may be esme.lora.LoRA wrappers
+        self._qlora = False         # set by ESM2.add_lora(quantized_base=True): adapters run and train over quantised q / k / v / out
 
     # -- weight layout ------------------------------------------------------
     def _pack_key(self):
@@ -568,13 +576,16 @@ class FlashMultiheadAttention(nn.Module):
         from esme._hip_attn_bwd import SUPPORTED_HEAD_DIMS
         from esme.lora import LoRA
         ag.refuse(self.padded, 'the padded layout (ESM2-35M: head dim 24, a width that is not a multiple of 64) has no backward')
-        ag.refuse(self._q4_qkv is not None or self._q4_out is not None, 'quantised weights have no backward (load the model without quantization=)')
+        ag.refuse((self._q4_qkv is not None or self._q4_out is not None) and not self._qlora,
+                  f'quantised weights have no backward (load the model without quantization=; {ag.QLORA_HINT})')
+        ag.check_frozen_norms((('self_attn.norm', self.norm), *((('self_attn.layernorm_q', self.layernorm_q), ('self_attn.layernorm_k', self.layernorm_k))
+                                                                 if self.pre_layernorm else ())), self._qlora and self._q4_qkv is not None)
         ag.refuse(self.head_dim not in SUPPORTED_HEAD_DIMS, f'head dim {self.head_dim}: the attention backward serves head dims {SUPPORTED_HEAD_DIMS}')
         ag.refuse(self.dropout != 0.0, 'attention dropout > 0 is not implemented')
         for p in ('q', 'k', 'v', 'out'):
             m = getattr(self, p)
             ag.refuse(isinstance(m, LoRA) and m.dropout_p > 0, f'LoRA dropout_p = {getattr(m, "dropout_p", 0)} > 0 is not implemented (dropout is out of scope)')
-            ag.check_linear(m.layer if isinstance(m, LoRA) else m, f'self_attn.{p}')
+            ag.check_linear(m.layer if isinstance(m, LoRA) else m, f'self_attn.{p}', self._qlora)
 
     def forward_trainable(self, x, cu_lens, max_len, lora_names=None, pos=None):
         """The attention branch (without the residual) as a differentiable function of x and of the adapters `lora_names` selects
@@ -602,19 +613,40 @@ class FlashMultiheadAttention(nn.Module):
         selection:  {'qkv': (X, A, c1A, bA, [W | s B | 0]) or None, 'out': (X, A, [W_o | s B | 0]) or None}.  The A matrices of all selected
         adapters of q, k and v are stacked to one (R, E) operand of esme_hip_lora_down; s B of each sits in the rows of its own
         projection, zero elsewhere.  `fold`: for the LayerNorm-folded QKV GEMM, whose epilogue multiplies the accumulator by rstd -- A
-        carries gamma (A' = bf16(gamma * A)), c1A = rowsum(A'), bA = A beta, and the kernel writes LN(x) A^T / rstd."""
+        carries gamma (A' = bf16(gamma * A)), c1A = rowsum(A'), bA = A beta, and the kernel writes LN(x) A^T / rstd.
+        On a quantised base that opted in (add_lora(quantized_base=True)) no bf16 copy of W is built: the last element of either tuple is
+        an ExtBlock, the (rows, X) extension columns [s B | 0] alone, keyed as above minus the base weight; _lora_extended puts it next to
+        the base in the weight scratch per call."""
         from esme.lora import LoRA, ext_width
         if self.padded:
             raise NotImplementedError('LoRA adapters are not implemented for padded layouts (head dim 24 / a width that is not a multiple of 64)')
-        if self._q4_qkv is not None or self._q4_out is not None:
-            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters)')
+        quantised = self._q4_qkv is not None or self._q4_out is not None
+        if quantised and not self._qlora:
+            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters, '
+                                      'unless they were attached with add_lora(quantized_base=True))')
         mods = {p: getattr(self, p) for p in ('q', 'k', 'v', 'out') if isinstance(getattr(self, p), LoRA)}
         sel = {p: m.select(lora_names) for p, m in mods.items()}
         params = [t for p, m in mods.items() for t in m.params(sel[p])]
-        base = (self._pack_fold() if fold else self._pack())[0]
-        key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), self._derived.key('fold' if fold else 'pack'),
-               _version_key(self.out.weight, *params))
         E = self.embed_dim
+        if quantised:
+            # the key of the unquantised form minus the base weight; the folded A' carries the LayerNorm, so its version stays
+            key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), 'quantised base',
+                   _version_key(*params, *((self.norm.weight, self.norm.bias) if fold else ())))
+            base = None
+        else:
+            base = (self._pack_fold() if fold else self._pack())[0]
+            key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), self._derived.key('fold' if fold else 'pack'),
+                   _version_key(self.out.weight, *params))
+
+        def extended(w, rows, X):
+            """(the weight form, its extension columns as a view): (rows, E + X) zeros with the base `w` in the first E columns; on a
+            quantised base (`w` None) an ExtBlock, the (rows, X) columns alone."""
+            if w is None:
+                we = ExtBlock(torch.zeros(rows, X, dtype=torch.bfloat16, device=self.norm.weight.device))
+                return we, we.block
+            we = torch.zeros(rows, E + X, dtype=torch.bfloat16, device=w.device)
+            we[:, :E] = w
+            return we, we[:, E:]
 
         def build():
             res = {'qkv': None, 'out': None}
@@ -628,23 +660,32 @@ class FlashMultiheadAttention(nn.Module):
                     A = (Af * self.norm.weight.data.float().unsqueeze(0)).to(torch.bfloat16).contiguous()
                     c1A = A.float().sum(dim=1).contiguous()
                     bA = (Af @ self.norm.bias.data.float()).contiguous() if self.norm.bias is not None else torch.zeros_like(c1A)
-                we = torch.zeros(3 * E, E + X, dtype=torch.bfloat16, device=base.device)
-                we[:, :E] = base
-                o = E
+                we, ext = extended(base, 3 * E, X)
+                o = 0
                 for i, a, b in blocks:
-                    we[i * E:(i + 1) * E, o:o + a.shape[0]] = b.to(torch.bfloat16)
+                    ext[i * E:(i + 1) * E, o:o + a.shape[0]] = b.to(torch.bfloat16)
                     o += a.shape[0]
                 res['qkv'] = (X, A, c1A, bA, we)
             if 'out' in mods:
                 A, B = mods['out'].stacked(sel['out'])
                 X = ext_width(A.shape[0])
-                wo = self.out.weight.data
-                we = torch.zeros(E, E + X, dtype=torch.bfloat16, device=wo.device)
-                we[:, :E] = wo
-                we[:, E:E + B.shape[1]] = B.to(torch.bfloat16)
+                we, ext = extended(None if quantised else self.out.weight.data, E, X)
+                ext[:, :B.shape[1]] = B.to(torch.bfloat16)
                 res['out'] = (X, A.contiguous(), we)
             return res
         return self._derived.get('lora', key, build)
+
+    def _lora_extended(self, which: str, entry, fold: bool = False):
+        """[W | s B | 0] of the _lora_weights entry of the GEMM `which` ('qkv' / 'out'): the cached tensor, or, on a quantised base, the base
+        expanded into a (rows, K + X) view of the shared weight scratch (esme.quantization.Q4Matrix) with the cached extension block copied
+        into the columns K .. K + X - 1 -- per call, like every use of a quantised weight; the GEMM that reads it is next on the stream."""
+        we = entry[-1]
+        if not isinstance(we, ExtBlock):
+            return we
+        q4 = self._q4_qkv if which == 'qkv' else self._q4_out
+        w = (q4.folded(entry[0]) if fold else q4.plain(entry[0]))[0]
+        w[:, q4.cols:].copy_(we.block)
+        return w
 
     def lora_ext_widths(self, lora_names):
         """(X of the QKV GEMM, X of the out-projection) for this selection (0: that GEMM has no adapter)."""
@@ -654,31 +695,36 @@ class FlashMultiheadAttention(nn.Module):
     def _qkv_lora_unfused(self, x, lw, rot):
         """LayerNorm kernel -> [h | h A^T] -> plain QKV GEMM over [W | s B] (the stage form, and the path without LayerNorm fold);
         without adapters (`lw` None or no q / k / v adapter selected) LayerNorm kernel -> plain QKV GEMM."""
-        w, b, _, _ = self._weights_qkv(False)
         if lw is None or lw['qkv'] is None:
+            w, b, _, _ = self._weights_qkv(False)
             return _hip.gemm_fused(self.norm(x), w, b, rot=rot)
-        X, A, _, _, we = lw['qkv']
+        X, A = lw['qkv'][:2]
         E = self.embed_dim
         he = torch.empty(x.shape[0], E + X, dtype=torch.bfloat16, device=x.device)
         self.norm(x, out=he[:, :E])
         _hip.lora_down(he[:, :E], A, he[:, E:])
-        return _hip.gemm_fused(he, we, b, rot=rot)
+        b = self._q4_qkv.bias if self._q4_qkv is not None else self._pack()[1]
+        return _hip.gemm_fused(he, self._lora_extended('qkv', lw['qkv']), b, rot=rot)
 
     def _qkv_operands(self, x, x_stats, ctx, lw, f16, pair_ext):
         """(operand, W', c1, c2) of the LayerNorm-folded QKV GEMM.  With q / k / v adapters (`lw`: _lora_weights): the operand is [x | u] with
         u = the adapters' down-projection, written here by esme_hip_lora_down, and W' = [W' | s B | 0].  With every lora_B zero the extension
         adds exact zeros to the fp32 accumulators, so the result equals the block's without adapters bit for bit."""
-        wf, _, c1, c2 = self._weights_qkv(True, f16, pair_ext)
         if lw is None or lw['qkv'] is None:
+            wf, _, c1, c2 = self._weights_qkv(True, f16, pair_ext)
             return x, wf, c1, c2
-        X, A, c1A, bA, wf = lw['qkv']
+        if self._q4_qkv is not None:                           # (the base is expanded once, below, next to its extension)
+            c1, c2 = self._q4_qkv.c1, self._q4_qkv.c2
+        else:
+            _, _, c1, c2 = self._weights_qkv(True, f16, pair_ext)
+        X, A, c1A, bA = lw['qkv'][:4]
         E = self.embed_dim
         xe = ctx.lora_x if ctx is not None else None
         if xe is None or xe.data_ptr() != x.data_ptr() or xe.stride(0) != x.stride(0) or xe.shape[1] < E + X:
             xe = torch.empty(x.shape[0], E + X, dtype=torch.bfloat16, device=x.device)       # (a caller outside the model's forward: x moves once)
             xe[:, :E].copy_(x)
         _hip.lora_down(xe[:, :E], A, xe[:, E:E + X], ln=(x_stats, self.embed_dim, self.norm.eps, c1A, bA))
-        return xe[:, :E + X], wf, c1, c2
+        return xe[:, :E + X], self._lora_extended('qkv', lw['qkv'], True), c1, c2
 
     def _out_operands(self, lw, f16, q, k, v, *attn_args, **attn_kw):
         """Runs the attention kernel (_attn) and returns (its output, W_o, b_o), the operands of the out-projection.  With an out adapter
@@ -686,12 +732,12 @@ class FlashMultiheadAttention(nn.Module):
         W_o = [W_o | s B | 0]."""
         if lw is None or lw['out'] is None:
             return (self._attn(q, k, v, *attn_args, **attn_kw), *self._weights_out(f16))
-        X, A, wo = lw['out']
+        X, A = lw['out'][:2]
         E = self.embed_dim
-        a = torch.empty(q.shape[0], E + X, dtype=torch.bfloat16, device=wo.device)
+        a = torch.empty(q.shape[0], E + X, dtype=torch.bfloat16, device=q.device)
         self._attn(q, k, v, *attn_args, out=a[:, :E], **attn_kw)
         _hip.lora_down(a[:, :E], A, a[:, E:])
-        return a, wo, self.out.bias
+        return a, self._lora_extended('out', lw['out']), self.out.bias
 
 
 class SwiGLU(nn.Module):
@@ -753,6 +799,7 @@ class FlashTransformerLayer(nn.Module):
         self.final_activation = final_activation
         self._q4_up = None          # esme.quantization.Q4Matrix pair when the layer is 4-bit
         self._q4_down = None
+        self._qlora = False         # set by ESM2.add_lora(quantized_base=True): forward_trainable runs over the quantised FFN projections
 
     def _fold_operands(self):
         ln = self.final[0]
@@ -905,21 +952,30 @@ class FlashTransformerLayer(nn.Module):
         wd, bd = self._weights_down()
         _hip.gemm_fused(mid, wd, bd, _hip.EPI_RESIDUAL, None, alpha, x16, resid32=x32, split_a=True)
 
+    def check_trainable(self):
+        """NotImplementedError, by name, for what forward_trainable cannot differentiate in this layer (the attention block's own
+        list: FlashMultiheadAttention.check_trainable)."""
+        from esme import autograd as ag
+        quantised = any(q is not None for q in (self._q4_up, self._q4_down))
+        ag.refuse(quantised and not self._qlora, f'quantised weights have no backward (load the model without quantization=; {ag.QLORA_HINT})')
+        ag.check_frozen_norms((('final.0', self.final[0]),), self._qlora and quantised)
+        self.self_attn.check_trainable()
+
     def forward_trainable(self, x, cu_lens, max_len, lora_names=None, pos=None):
         """x + attn(x) / s, then x + ffn(x) / s (reference attention.py:253-255) with a grad_fn: the attention branch of
         FlashMultiheadAttention.forward_trainable, the FFN (GELU / SwiGLU) in torch ops around frozen projections."""
         from esme import autograd as ag
-        ag.refuse(any(q is not None for q in (self._q4_up, self._q4_down)), 'quantised weights have no backward (load the model without quantization=)')
+        self.check_trainable()
         x = x + self.self_attn.forward_trainable(x, cu_lens, max_len, lora_names, pos) / self.residue_scaling
         h = ag.layer_norm(x, self.final[0])
         if self.final_activation == 'gelu':
             for lin in (self.final[1], self.final[3]):
-                ag.check_linear(lin, 'the FFN')
+                ag.check_linear(lin, 'the FFN', self._qlora)
             y = ag.frozen_linear(torch.nn.functional.gelu(ag.frozen_linear(h, self.final[1], True)), self.final[3], True)
         else:
             sw = self.final[1]
             for lin in (sw.activation, sw.fc, self.final[2]):
-                ag.check_linear(lin, 'the FFN')
+                ag.check_linear(lin, 'the FFN', self._qlora)
             y = ag.frozen_linear(torch.nn.functional.silu(ag.frozen_linear(h, sw.activation, True)) * ag.frozen_linear(h, sw.fc, True), self.final[2], True)
         return x + y / self.residue_scaling
 

@@ -7,6 +7,9 @@
    against W^T from the derived-weight cache (esme.nn.weight_t).
  - `TrainableLinear`: a layer's own projection whose weight requires grad (model.mark_trainable): the same forward and dX, and
    (dW, db) = esme_hip_gemm_wgrad (include/esme_hip_gemm_wgrad.h) in bfloat16, the parameters' dtype.
+ - `QuantFrozenLinear`: a frozen projection stored as 4-bit / int8 codes (a model that opted in with add_lora(quantized_base=True)):
+   W and, in the backward, W^T are expanded from the codes into the model's one weight scratch each time they are used
+   (include/esme_hip_dequant_t.h); no bf16 copy of either is kept.
 
  - `AttentionPooling`: forward = esme_hip_attn_pool on the folded queries U, backward = esme_hip_attn_pool_bwd
    (include/esme_hip_attn_pool_bwd.h); `pool_fold` is the fold itself in fp32 torch ops, so that autograd carries dU on to the class
@@ -101,6 +104,35 @@ class TrainableLinear(torch.autograd.Function):
         return dx, (dw if ctx.needs_input_grad[1] else None), db, None
 
 
+class QuantFrozenLinear(torch.autograd.Function):
+    """y = x W^T + b for a quantised projection `qlin` (esme.quantization.Linear4bit / Linear8bit), which takes no gradient: the forward
+    expands W from the codes into `scratch` (the model's one WeightScratch) and runs the GEMM kernel on it; the backward expands W^T
+    from the same codes (esme_hip_dequantize_*_t) into the same buffer and runs dX = dY W on the same kernel against it.  Nothing of weight
+    size is saved or cached: the context holds references to the module and the scratch only.
+
+    One buffer suffices because an expansion and the GEMM that consumes it are enqueued back to back on one stream: whatever is
+    expanded next (another projection's forward, a recomputed forward under checkpoint_layers=True in the middle of the backward)
+    is ordered after that GEMM.  This rests on every launch going to ONE stream, so the backward refuses to run on another one
+    than the forward's (autograd runs a node's backward on its forward's stream; the check names what broke if that ever changes)."""
+
+    @staticmethod
+    def forward(ctx, x, qlin, scratch):
+        N, K = qlin.out_features, qlin.in_features
+        w = qlin.dequantize(out=scratch.view(N, K, x.device))
+        ctx.qlin, ctx.scratch, ctx.stream = qlin, scratch, _hip._stream()
+        return _hip.gemm(x if x.stride(-1) == 1 else x.contiguous(), w, qlin.bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        qlin = ctx.qlin
+        if _hip._stream() != ctx.stream:
+            raise RuntimeError('QuantFrozenLinear: the backward runs on another stream than the forward; the shared weight scratch is '
+                               'ordered by ONE stream (run forward_trainable and backward under the same torch.cuda.stream)')
+        dy = _kernel_rows(dy)
+        wt = qlin.dequantize_t(out=ctx.scratch.view(qlin.in_features, qlin.out_features, dy.device))
+        return _hip.gemm(dy, wt), None, None
+
+
 class AttentionPooling(torch.autograd.Function):
     """out (B, n_cls, E) = attention pooling of embed (T, E) bfloat16 / float32 with the folded queries U (n_cls * heads, E) float32
     (`pool_fold`); differentiable in embed and U."""
@@ -176,9 +208,12 @@ def check_head_input(x: torch.Tensor, params, what: str) -> None:
 def frozen_linear(x: torch.Tensor, lin, layer_projection: bool = False) -> torch.Tensor:
     """lin(x) for a 2-D bfloat16 x, differentiable in x (and in lin's parameters where they require grad).  The kernels serve a
     bfloat16 projection whose two widths are multiples of 64 (the GEMM's K tile, the weight-gradient kernel's wave tile): frozen, it is
-    `FrozenLinear`; trained (model.mark_trainable) and one of a layer's own projections (`layer_projection`: q, k, v, out, FFN up /
+    `FrozenLinear` (`QuantFrozenLinear` when it is stored quantised); trained (model.mark_trainable) and one of a layer's own projections (`layer_projection`: q, k, v, out, FFN up /
     down, SwiGLU's two), it is `TrainableLinear`.  Any other trainable projection (the LM head after mark_lmhead) and any other shape
     (the vocabulary projection: dX = dY W has K = vocab_size) is torch's F.linear."""
+    if _is_quantised(lin):                                # (check_linear let it through: the model opted in)
+        refuse(getattr(lin, 'scratch', None) is None, 'a quantised projection outside a quantised model has no weight scratch (quantize_model_ sets it)')
+        return QuantFrozenLinear.apply(x, lin, lin.scratch)
     w, b = lin.weight, lin.bias
     trainable = w.requires_grad or (b is not None and b.requires_grad)
     if w.shape[0] % 64 or w.shape[1] % 64 or (trainable and not layer_projection):
@@ -229,6 +264,28 @@ def refuse(cond: bool, what: str) -> None:
         raise NotImplementedError(f'forward_trainable: {what}')
 
 
-def check_linear(lin, what: str) -> None:
-    """Quantised storage has no backward here: name it."""
-    refuse(lin.weight.dtype != torch.bfloat16, f'{what} is stored quantised ({lin.weight.dtype}); training needs unquantised bfloat16 base weights')
+QLORA_HINT = 'adapters train over a quantised base after model.add_lora(quantized_base=True)'
+
+
+def _is_quantised(lin) -> bool:
+    from esme.quantization import Linear4bit, Linear8bit
+    return isinstance(lin, (Linear4bit, Linear8bit))
+
+
+def check_linear(lin, what: str, qlora: bool = False) -> None:
+    """Quantised storage has a backward (QuantFrozenLinear) only where the model opted in (`qlora`): name it otherwise."""
+    if qlora and _is_quantised(lin):
+        return
+    refuse(lin.weight.dtype != torch.bfloat16, f'{what} is stored quantised ({lin.weight.dtype}); training needs unquantised bfloat16 base weights ({QLORA_HINT})')
+
+
+def check_frozen_norms(norms, qlora: bool) -> None:
+    """On a quantised base the LayerNorms stay frozen: the quantised matrices of the fused inference forward snapshot the LayerNorm
+    gain and the folded constants c1 / c2 when they are built (esme.quantization.Q4Matrix), so a trained LayerNorm would leave
+    model.eval(); model(...) stale.  `norms`: (name, module) pairs."""
+    if not qlora:
+        return
+    for name, ln in norms:
+        for pn, p in ln.named_parameters(recurse=False):
+            refuse(p.requires_grad, f'{name}.{pn} requires grad on a quantised base: the quantised inference forward keeps a snapshot of the '
+                   'LayerNorms, so only the adapters and the LM head (mark_lmhead) train here')

@@ -693,12 +693,17 @@ class ESM2(nn.Module):
         ctx.lora_x[:, :E].copy_(x)                                # (row move, no arithmetic)
         return ctx.lora_x[:, :E]
 
-    def add_lora(self, rank=16, alpha=16, layers=('query', 'value', 'output'), dropout_p=0., adapter_names=None):
+    def add_lora(self, rank=16, alpha=16, layers=('query', 'value', 'output'), dropout_p=0., adapter_names=None, quantized_base=False):
         """Attach LoRA adapters (reference esm.py:495-543): every layer's `self_attn.{q,k,v,out}` named in `layers` becomes an
         esme.lora.LoRA around the projection, with one (A, B) pair per name in `adapter_names` (default ['default']); A is initialised
         like the reference's (Kaiming uniform), B with zeros, so fresh adapters leave the model's output unchanged.  Inference only:
         `dropout_p` is stored (and written by save_lora) but never applied.  Refuses what cannot run the adapters: a precision other
-        than 'fast', quantised base weights, padded layouts (ESM2-35M), ranks outside 1 .. 64."""
+        than 'fast', quantised base weights, padded layouts (ESM2-35M), ranks outside 1 .. 64.
+        `quantized_base=True` opts a model loaded with `quantization=` in (QLoRA; on an unquantised model it changes nothing): the
+        adapters are attached around the 4-bit / int8 projections, `forward_trainable` trains them (and the LM head after
+        mark_lmhead) with the base expanded from the codes in forward and backward (esme.autograd.QuantFrozenLinear), and the fused
+        inference forward runs them with the extension block placed next to the expanded base per call.  The codes are not
+        trainable and the LayerNorms stay frozen (mark_trainable / a LayerNorm that requires grad keep raising)."""
         from esme.lora import LoRA
         wanted = set(layers)
         assert len(wanted.difference({'query', 'value', 'key', 'output'})) == 0, 'layers must be a subset of {"query", "value", "key", "output"}'
@@ -706,8 +711,10 @@ class ESM2(nn.Module):
             raise NotImplementedError('LoRA adapters are already attached to this model (a second set would wrap the first)')
         if self.precision != 'fast':
             raise NotImplementedError(f"precision {self.precision!r} has no LoRA adapter path: adapters run in precision 'fast' only")
-        if getattr(self, 'quantization', None) is not None:
-            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters)')
+        quantised = getattr(self, 'quantization', None) is not None
+        if quantised and not quantized_base:
+            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters; '
+                                      'opt in to adapters over the quantised base with add_lora(quantized_base=True))')
         if self.padded:
             raise NotImplementedError('LoRA adapters are not implemented for padded layouts (head dim 24 / a width that is not a multiple of 64: ESM2-35M)')
         if not (1 <= int(rank) <= 64) or int(rank) != rank:
@@ -720,7 +727,9 @@ class ESM2(nn.Module):
                 if long in wanted:
                     setattr(att, short, LoRA(getattr(att, short), rank=rank, alpha=alpha, dropout_p=dropout_p, names=adapter_names))
             att._has_lora = True
+            att._qlora = layer._qlora = bool(quantised)      # (quantised here means: and opted in)
         self.__dict__['_lora_attached'] = True
+        self._qlora = bool(quantised)
         self.mark_only_lora_as_trainable(adapter_names)
         self.invalidate_graphs()
         return self
@@ -747,17 +756,17 @@ class ESM2(nn.Module):
                    'layers': ','.join(kw['layers']), 'names': ','.join(names), 'format': 'pt'})
         return self
 
-    def load_lora(self, path: str, names=None):
+    def load_lora(self, path: str, names=None, quantized_base=False):
         """Attach the adapters of a file written by `save_lora` (this package's or the reference's) to a model loaded from the base
         checkpoint (esm.py:587-608).  `names` is accepted for signature compatibility; as in the reference, every adapter of the file
-        is attached -- select per call with `lora_names=`."""
+        is attached -- select per call with `lora_names=`.  `quantized_base`: as in add_lora."""
         from safetensors import safe_open
         with safe_open(path, framework='pt', device='cpu') as f:
             md = f.metadata() or {}
             tensors = {k: f.get_tensor(k) for k in f.keys()}
         a = md['alpha']
         self.add_lora(rank=int(md['rank']), alpha=int(a) if a.lstrip('-').isdigit() else float(a), dropout_p=float(md['dropout_p']),
-                      layers=md['layers'].split(','), adapter_names=md['names'].split(','))
+                      layers=md['layers'].split(','), adapter_names=md['names'].split(','), quantized_base=quantized_base)
         own = self.state_dict()
         unexpected = [k for k in tensors if k not in own]
         assert len(unexpected) == 0, f'Expected LoRA keys in the model missing state_dict: {unexpected}'
@@ -781,17 +790,21 @@ class ESM2(nn.Module):
         layers' inputs are kept and each layer is recomputed in the backward -- the reference's `checkpointing=`; every kernel on the
         path is deterministic, so loss and gradients are bit-equal with and without it.  The same in train() and eval() (there is no
         dropout).  `model.train(); model(...)` still raises: the fused inference forward has no backward.  NotImplementedError, by
-        name, for a precision other than 'fast', quantised weights, the padded ESM2-35M layout, dropout > 0, a head dim outside
+        name, for a precision other than 'fast', quantised weights (unless add_lora(quantized_base=True) opted in: then the adapters
+        and the LM head train over the quantised base, and a LayerNorm that requires grad is refused), the padded ESM2-35M layout, dropout > 0, a head dim outside
         {32, 64}, the learned-position ESM-1 models and a token embedding that requires grad (its kernel has no backward)."""
         from esme import autograd as ag
         ag.refuse(self.embed_tokens.weight.requires_grad, 'embed_tokens.weight requires grad, but the token embedding has no backward: '
                   'select what to train with model.mark_trainable() (projections and LayerNorms), which leaves the embedding frozen')
         ag.refuse(self.precision != 'fast', f"precision {self.precision!r} has no backward: training runs in precision 'fast' only")
-        ag.refuse(getattr(self, 'quantization', None) is not None, 'quantised weights have no backward (load the model without quantization=)')
+        qlora = bool(getattr(self, '_qlora', False))
+        ag.refuse(getattr(self, 'quantization', None) is not None and not qlora,
+                  f'quantised weights have no backward (load the model without quantization=; {ag.QLORA_HINT})')
+        ag.check_frozen_norms((('emb_layer_norm_after', self.emb_layer_norm_after),), qlora)
         ag.refuse(self.padded, 'the padded layout (ESM2-35M: head dim 24, a width that is not a multiple of 64) has no backward')
         ag.refuse(type(self)._embedding_phys is not ESM2._embedding_phys, 'the learned-position models (ESM-1b / ESM-1v) are not covered')
         for layer in self.layers:
-            layer.self_attn.check_trainable()
+            layer.check_trainable()
         if self.has_lora and lora_names:
             have = self.lora_names()
             for n in lora_names:

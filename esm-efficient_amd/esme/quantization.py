@@ -31,7 +31,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from esme import _hip
+from esme import _hip, _hip_dequant_t
 
 # 16-entry codebooks, values in [-1, 1].  'fp4': sign + {0, 1/192, 1/6, 1/4, 1/3, 1/2, 2/3, 1}
 # in the index order of the e2m1-style code bitsandbytes publishes; 'nf4': the normal-float
@@ -98,13 +98,20 @@ class Q4Matrix:
             return _hip.dequantize_8bit(self.codes, self.absmax, col_scale=col_scale, out=out)
         return _hip.dequantize_4bit(self.codes, self.absmax, self.codebook, col_scale=col_scale, out=out)
 
-    def plain(self):
-        """(W bf16 in scratch, bias)"""
-        return self._expand(None, self.scratch.view(self.rows, self.cols, self.codes.device)), self.bias
+    def _expand_ext(self, col_scale, ext: int):
+        """The expansion into the first `cols` columns of a (rows, cols + ext) scratch view; returns the whole view.  The `ext` columns
+        (the extension K-tile of LoRA adapters over a quantised base: esme.attention._lora_weights) are the caller's to fill."""
+        view = self.scratch.view(self.rows, self.cols + ext, self.codes.device)
+        self._expand(col_scale, view[:, :self.cols] if ext else view)
+        return view
 
-    def folded(self):
-        """(W' = W diag(gamma) bf16 in scratch, c1, c2)"""
-        return self._expand(self.gamma, self.scratch.view(self.rows, self.cols, self.codes.device)), self.c1, self.c2
+    def plain(self, ext: int = 0):
+        """(W bf16 in scratch, bias); `ext`: ([W | ext uninitialised columns], bias)"""
+        return self._expand_ext(None, ext), self.bias
+
+    def folded(self, ext: int = 0):
+        """(W' = W diag(gamma) bf16 in scratch, c1, c2); `ext`: as in plain()"""
+        return self._expand_ext(self.gamma, ext), self.c1, self.c2
 
 
 class Linear4bit(nn.Module):
@@ -120,6 +127,7 @@ class Linear4bit(nn.Module):
         self.weight = nn.Parameter(codes, requires_grad=False)
         self.register_buffer('absmax', absmax)
         self.bias = nn.Parameter(bias, requires_grad=False) if bias is not None else None
+        self.scratch: Optional[WeightScratch] = None      # the model's shared scratch (quantize_layer_): esme.autograd.QuantFrozenLinear expands into it
 
     @classmethod
     def from_linear(cls, linear, quant_type: str = 'fp4') -> 'Linear4bit':
@@ -128,6 +136,10 @@ class Linear4bit(nn.Module):
 
     def dequantize(self, out=None) -> torch.Tensor:
         return _hip.dequantize_4bit(self.weight.data, self.absmax, codebook_of(self.quant_type), out=out)
+
+    def dequantize_t(self, out=None) -> torch.Tensor:
+        """W^T (in_features, out_features) bf16 straight from the codes: bit for bit dequantize().t()."""
+        return _hip_dequant_t.dequantize_4bit_t(self.weight.data, self.absmax, codebook_of(self.quant_type), out=out)
 
     def forward(self, x, epilogue=_hip.EPI_NONE, resid=None, alpha=1.0, out=None):
         shape = x.shape
@@ -151,6 +163,7 @@ class Linear8bit(nn.Module):
         self.weight = nn.Parameter(codes, requires_grad=False)
         self.register_buffer('absmax', scale)
         self.bias = nn.Parameter(bias, requires_grad=False) if bias is not None else None
+        self.scratch: Optional[WeightScratch] = None      # as Linear4bit.scratch
 
     @property
     def cweight(self):
@@ -167,6 +180,10 @@ class Linear8bit(nn.Module):
 
     def dequantize(self, out=None) -> torch.Tensor:
         return _hip.dequantize_8bit(self.weight.data, self.absmax, out=out)
+
+    def dequantize_t(self, out=None) -> torch.Tensor:
+        """W^T (in_features, out_features) bf16 straight from the codes: bit for bit dequantize().t()."""
+        return _hip_dequant_t.dequantize_8bit_t(self.weight.data, self.absmax, out=out)
 
     def forward(self, x, epilogue=_hip.EPI_NONE, resid=None, alpha=1.0, out=None):
         shape = x.shape
@@ -231,6 +248,8 @@ def quantize_layer_(layer, quant_type: str, scratch: WeightScratch):
         layer._q4_down = Q4Matrix(down.weight.data, down.absmax, down.bias.data if down.bias is not None else None,
                                   quant_type, scratch)
         layer._derived.clear()
+        for m in (*q4, down, *((up,) if layer.final_activation == 'gelu' else (gate, fc))):
+            m.scratch = scratch
     return layer
 
 
