@@ -112,6 +112,35 @@ def padding_mask(cu_lens: torch.Tensor, max_len: int) -> torch.Tensor:
     return cols < lengths
 
 
+def mask_tokens(token: torch.Tensor, freq: float = 0.15, alter: float = 0.1, alphabet=Alphabet3
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """BERT-style corruption for the masked-token objective: `(masked_tokens, mask)` for 1-D packed or 2-D padded ids.
+
+    `mask` (bool, the shape of `token`) selects the positions the loss is taken at: every position that is not `<cls>`, `<eos>` or
+    `<pad>` with probability `freq`, and at least one per row (a 1-D packed batch counts as one row; a row without any eligible
+    position stays empty).  A selected position becomes `<mask>`; then, with probability `alter`, a uniform id of the alphabet's
+    amino-acid range; then, with probability `alter` and independently of the step before, the original id again -- so it ends as
+    `<mask>` with probability (1 - alter)^2, as a random residue with alter (1 - alter) and as the original with alter.  `token` is
+    not modified.  Draws from torch's global generator (torch.manual_seed)."""
+    if token.ndim not in (1, 2):
+        raise ValueError('tokens must be 1D or 2D')
+    if token.numel() == 0:
+        return token.clone(), torch.zeros_like(token, dtype=torch.bool)
+    rows = token.reshape(1, -1) if token.ndim == 1 else token
+    eligible = (rows != alphabet.cls_idx) & (rows != alphabet.eos_idx) & (rows != alphabet.padding_idx)
+    mask = (torch.rand(rows.shape) < freq) & eligible
+    # a row the draw left empty gets one of its eligible positions, uniformly (argmax of random keys over the eligible ones)
+    keys = torch.rand(rows.shape).masked_fill(~eligible, -1.0)
+    forced = torch.zeros_like(mask)
+    forced[torch.arange(rows.shape[0]), keys.argmax(dim=1)] = True
+    mask = mask | (forced & eligible & ~mask.any(dim=1, keepdim=True))
+    lo, hi = alphabet.amino_acids_idx[0], alphabet.amino_acids_idx[-1] + 1
+    masked = torch.where(mask, torch.full_like(rows, alphabet.mask_idx), rows)
+    masked = torch.where(mask & (torch.rand(rows.shape) < alter), torch.randint(lo, hi, rows.shape, dtype=rows.dtype), masked)
+    masked = torch.where(mask & (torch.rand(rows.shape) < alter), rows, masked)
+    return masked.reshape(token.shape), mask.reshape(token.shape)
+
+
 def pad_tokens(tokens: List[torch.Tensor], alphabet=Alphabet3) -> torch.Tensor:
     """Right-pad a list of token tensors to a common length and stack them: 1-D items -> (B, L),
     (1, L_i) items -> (B, L) (reference alphabet.py:186-213)."""

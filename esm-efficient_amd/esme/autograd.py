@@ -10,6 +10,9 @@
  - `QuantFrozenLinear`: a frozen projection stored as 4-bit / int8 codes (a model that opted in with add_lora(quantized_base=True)):
    W and, in the backward, W^T are expanded from the codes into the model's one weight scratch each time they are used
    (include/esme_hip_dequant_t.h); no bf16 copy of either is kept.
+ - `TokenEmbedding`: the token-embedding lookup of a model that opted in with mark_trainable(embedding=True): forward =
+   esme_hip_embed, backward = esme_hip_embed_bwd (include/esme_hip_embed_bwd.h): per table row the fp32 sum of its rows of dX in a fixed
+   order, without atomics.
 
  - `AttentionPooling`: forward = esme_hip_attn_pool on the folded queries U, backward = esme_hip_attn_pool_bwd
    (include/esme_hip_attn_pool_bwd.h); `pool_fold` is the fold itself in fp32 torch ops, so that autograd carries dU on to the class
@@ -26,7 +29,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_gemm_wgrad
+from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_gemm_wgrad
 from esme.nn import weight_t
 
 
@@ -56,6 +59,24 @@ class VarlenAttention(torch.autograd.Function):
         max_len, heads, scale = ctx.args
         dq, dk, dv = _hip_attn_bwd.attn_varlen_bwd(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], o, d_o, cu_lens, max_len, heads, scale)
         return dq, dk, dv, None, None, None, None
+
+
+class TokenEmbedding(torch.autograd.Function):
+    """x (T, E) = the rows table[tokens] for packed int64 ids (T,), zero rows for `mask_idx` / `pad_idx` (-1: none) and for ids outside
+    the table; differentiable in `table` (V, E) bfloat16.  The excluded rows of the table get a zero gradient: they do not reach x."""
+
+    @staticmethod
+    def forward(ctx, table, tokens, mask_idx, pad_idx):
+        tokens = tokens.contiguous()
+        ctx.save_for_backward(tokens)
+        ctx.args = (table.shape[0], int(mask_idx), int(pad_idx))
+        return _hip.embed(tokens, table.detach(), mask_idx=int(mask_idx), pad_idx=int(pad_idx))
+
+    @staticmethod
+    def backward(ctx, d_x):
+        tokens, = ctx.saved_tensors
+        V, mask_idx, pad_idx = ctx.args
+        return _hip_embed_bwd.embed_bwd(_kernel_rows(d_x), tokens, V, mask_idx, pad_idx), None, None, None
 
 
 class FrozenLinear(torch.autograd.Function):

@@ -2,9 +2,10 @@
 
 The caller side of the hot path: `FastaTokenDataset[i]` is exactly the
 `(tokens, (cu_lens, max_len))` pair `ESM2.forward` consumes.  Names, arguments and the
-greedy packing rule follow `esme/data.py:12-60,63-162` of the reference; the Lightning
-data modules and the masking datasets for training (data.py:165-520) are outside the
-inference hot path.
+greedy packing rule follow `esme/data.py:12-60,63-162` of the reference.  `MaskedFastaDataset` /
+`MaskedFastaTokenDataset` add the masked-token corruption of `esme.alphabet.mask_tokens` for
+masked-LM training (the reference's constructor arguments and item layouts, data.py:165-245);
+the Lightning data modules (data.py:247-520) stay out of scope.
 """
 from __future__ import annotations
 
@@ -12,7 +13,8 @@ from typing import List, Sequence
 
 from torch.utils.data import DataLoader, Dataset
 
-from esme.alphabet import Alphabet3, pad_tokens, tokenize, tokenize_unpad
+import torch
+from esme.alphabet import Alphabet3, mask_tokens, pad_tokens, tokenize, tokenize_unpad
 from esme.fasta import Fasta
 
 
@@ -109,3 +111,41 @@ class FastaTokenDataset(BaseFastaDataset):
         for it, while worker processes FORKED from a process that already holds a GPU context stall its queues for 1 - 3 s when they start
         (profiles/r05_e2e_fork_stall.txt); pass `multiprocessing_context='forkserver'` if workers are needed."""
         return DataLoader(self, num_workers=num_workers, batch_size=None, **kwargs)
+
+
+class MaskedFastaDataset(FastaDataset):
+    """One sequence per item with its masked-token corruption: `(tokens, masked_tokens, mask)`, each (1, L); `collate_fn` right-pads a
+    batch (`<pad>` for the ids, False for the mask).  `mask_freq` / `alter_freq`: `freq` / `alter` of esme.alphabet.mask_tokens."""
+
+    def __init__(self, fasta, fai=None, max_len=None, k_sample=None, mask_freq=.15, alter_freq=.1, alphabet=Alphabet3):
+        super().__init__(fasta, fai=fai, k_sample=k_sample, max_len=max_len, alphabet=alphabet)
+        self.mask_freq, self.alter_freq = mask_freq, alter_freq
+
+    def __getitem__(self, idx):
+        token = super().__getitem__(idx)
+        masked, mask = mask_tokens(token, self.mask_freq, self.alter_freq, alphabet=self.alphabet)
+        return token, masked, mask
+
+    def collate_fn(self, batch):
+        tokens = pad_tokens([b[0] for b in batch], alphabet=self.alphabet)
+        masked = pad_tokens([b[1] for b in batch], alphabet=self.alphabet)
+        mask = torch.zeros(tokens.shape, dtype=torch.bool)
+        for i, b in enumerate(batch):
+            mask[i, :b[2].numel()] = b[2].reshape(-1)
+        return tokens, masked, mask
+
+
+class MaskedFastaTokenDataset(FastaTokenDataset):
+    """Item i = the i-th token-budget batch, packed, with its masked-token corruption:
+    `(tokens, (cu_lens, max_len), masked_tokens, mask)` -- `masked_tokens` is the model's input, `tokens[mask]` the targets."""
+
+    def __init__(self, fasta, fai=None, token_per_batch=50_000, k_sample=None, max_len=None, mask_freq=.15, alter_freq=.1,
+                 drop_last=False, shuffle=True, random_state=None, alphabet=Alphabet3):
+        super().__init__(fasta, fai=fai, token_per_batch=token_per_batch, k_sample=k_sample, max_len=max_len, drop_last=drop_last,
+                         shuffle=shuffle, random_state=random_state, alphabet=alphabet)
+        self.mask_freq, self.alter_freq = mask_freq, alter_freq
+
+    def __getitem__(self, idx):
+        tokens, unpad_args = super().__getitem__(idx)
+        masked, mask = mask_tokens(tokens, self.mask_freq, self.alter_freq, alphabet=self.alphabet)
+        return tokens, unpad_args, masked, mask

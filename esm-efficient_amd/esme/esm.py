@@ -279,13 +279,17 @@ class ESM2(nn.Module):
 
     def _unpad(self, x, tokens):
         """Boolean-mask row gather: the `unpad_input` contract (esm.py:238)."""
+        indices, cu_lens, max_len = self._unpad_index(tokens)
+        return _hip.gather_rows(x.view(-1, x.shape[-1]), indices), indices, cu_lens, max_len
+
+    def _unpad_index(self, tokens):
+        """(flat indices of the rows that are not `<pad>`, cu_lens, max_len) of 2-D tokens."""
         keep = tokens.ne(self.alphabet.padding_idx)
         lens = keep.sum(dim=1, dtype=torch.int32)
         indices = torch.nonzero(keep.flatten(), as_tuple=False).flatten()
         cu_lens = torch.zeros(tokens.shape[0] + 1, dtype=torch.int32, device=tokens.device)
         cu_lens[1:] = torch.cumsum(lens, 0)
-        max_len = int(lens.max())
-        return _hip.gather_rows(x.view(-1, x.shape[-1]), indices), indices, cu_lens, max_len
+        return indices, cu_lens, int(lens.max())
 
     @staticmethod
     def _pad(x, indices, batch, seqlen):
@@ -792,9 +796,12 @@ class ESM2(nn.Module):
         dropout).  `model.train(); model(...)` still raises: the fused inference forward has no backward.  NotImplementedError, by
         name, for a precision other than 'fast', quantised weights (unless add_lora(quantized_base=True) opted in: then the adapters
         and the LM head train over the quantised base, and a LayerNorm that requires grad is refused), the padded ESM2-35M layout, dropout > 0, a head dim outside
-        {32, 64}, the learned-position ESM-1 models and a token embedding that requires grad (its kernel has no backward)."""
+        {32, 64}, the learned-position ESM-1 models and a token embedding that requires grad without mark_trainable(embedding=True)
+        (with it the table trains: esme.autograd.TokenEmbedding; quantised models stay refused)."""
         from esme import autograd as ag
-        ag.refuse(self.embed_tokens.weight.requires_grad, 'embed_tokens.weight requires grad, but the token embedding has no backward: '
+        train_emb = bool(self.__dict__.get('_train_embedding', False))
+        ag.refuse(self.embed_tokens.weight.requires_grad and not train_emb,
+                  'embed_tokens.weight requires grad, but the token embedding has no backward: '
                   'select what to train with model.mark_trainable() (projections and LayerNorms), which leaves the embedding frozen')
         ag.refuse(self.precision != 'fast', f"precision {self.precision!r} has no backward: training runs in precision 'fast' only")
         qlora = bool(getattr(self, '_qlora', False))
@@ -803,6 +810,8 @@ class ESM2(nn.Module):
         ag.check_frozen_norms((('emb_layer_norm_after', self.emb_layer_norm_after),), qlora)
         ag.refuse(self.padded, 'the padded layout (ESM2-35M: head dim 24, a width that is not a multiple of 64) has no backward')
         ag.refuse(type(self)._embedding_phys is not ESM2._embedding_phys, 'the learned-position models (ESM-1b / ESM-1v) are not covered')
+        ag.refuse(train_emb and getattr(self, 'quantization', None) is not None,
+                  'mark_trainable(embedding=True) on a quantised model: over a quantised base only the adapters and the LM head train')
         for layer in self.layers:
             layer.check_trainable()
         if self.has_lora and lora_names:
@@ -812,13 +821,27 @@ class ESM2(nn.Module):
                     raise KeyError(f'LoRA adapter {n!r} not found (available: {have})')
         names = tuple(lora_names) if lora_names else None
         with _hip.stream_scope(self.embed_tokens.weight.device):
-            x = self._embedding_phys(tokens, pad_args)
             if pad_args is not None:
                 assert tokens.ndim == 1, 'tokens are expected to be unpadded with shape (batch * seq_len)'
                 cu_lens, max_len = pad_args
             else:
                 assert tokens.ndim == 2, 'tokens are expected to be padded with shape (batch, seq_len, embed_dim)'
-                x, pad_indices, cu_lens, max_len = self._unpad(x, tokens)
+            if train_emb:
+                # the ids are packed BEFORE the lookup (the rows that are kept are the same rows): a `<pad>` row never reaches the
+                # lookup, so it contributes nothing to the table's gradient, and 2-D tokens give the packed gradients
+                if self.debug_checks:
+                    self.check_tokens(tokens)
+                if pad_args is None:
+                    pad_indices, cu_lens, max_len = self._unpad_index(tokens)
+                    tokens_packed = tokens.flatten()[pad_indices]
+                else:
+                    tokens_packed = tokens
+                x = ag.TokenEmbedding.apply(self.embed_tokens.weight, tokens_packed, self.alphabet.mask_idx if self.zero_mask_rows else -1,
+                                            self.alphabet.padding_idx if (pad_args is None and self.zero_mask_rows) else -1)
+            else:
+                x = self._embedding_phys(tokens, pad_args)
+                if pad_args is None:
+                    x, pad_indices, cu_lens, max_len = self._unpad(x, tokens)
             if cu_lens.dtype != torch.int32:
                 cu_lens = cu_lens.to(torch.int32)
             max_len = int(max_len)
@@ -840,15 +863,20 @@ class ESM2(nn.Module):
         return self
 
     # -- full fine-tuning (esme/autograd.py TrainableLinear, include/esme_hip_gemm_wgrad.h) --------------------------------------
-    def mark_trainable(self, projections=True, norms=True, layers=None):
+    def mark_trainable(self, projections=True, norms=True, layers=None, embedding=False):
         """Select what full fine-tuning trains through `forward_trainable`.  `projections`: requires_grad on the weights and biases of
         the selected layers' own projections (q, k, v, out, FFN up / down, SwiGLU's two; under a LoRA wrapper the base `layer`) --
         their gradients come from esme_hip_gemm_wgrad.  `norms`: on the selected layers' LayerNorms (ESM-C's q / k norms included) and,
         when `layers` is None, on `emb_layer_norm_after`, which belongs to no layer -- their gradients are torch's.  `layers`: indices
         (negative ones count from the end) for the "unfreeze the top k layers" recipe; None: all.  Every layer that is not selected
-        is frozen, so `mark_trainable(False, False)` freezes the backbone again.  The token embedding stays frozen (its kernel has no
-        backward), and the LM head and LoRA adapters keep their flags (mark_lmhead, mark_only_lora_as_trainable)."""
+        is frozen, so `mark_trainable(False, False)` freezes the backbone again.  `embedding=True` opts the token embedding in
+        (masked-LM training): requires_grad on `embed_tokens.weight`, and `forward_trainable` then runs the lookup as
+        esme.autograd.TokenEmbedding, whose backward is esme_hip_embed_bwd.  `embedding=False` (the default) withdraws the opt-in, and
+        clears the flag where the opt-in had set it; a flag set by hand is not touched, and `forward_trainable` keeps refusing it.  The
+        LM head and LoRA adapters keep their flags (mark_lmhead, mark_only_lora_as_trainable)."""
         from esme.lora import LoRA
+        if embedding and getattr(self, 'quantization', None) is not None:
+            raise NotImplementedError('mark_trainable(embedding=True): the token embedding does not train on a quantised model')
         L = len(self.layers)
         if layers is None:
             chosen = set(range(L))
@@ -880,6 +908,11 @@ class ESM2(nn.Module):
                     p.requires_grad_(bool(norms) and i in chosen)
         for p in self.emb_layer_norm_after.parameters(recurse=False):
             p.requires_grad_(bool(norms) and layers is None)
+        if embedding:
+            self.__dict__['_train_embedding'] = True
+            self.embed_tokens.weight.requires_grad_(True)
+        elif self.__dict__.pop('_train_embedding', False):
+            self.embed_tokens.weight.requires_grad_(False)
         return self
 
     # -- loading -------------------------------------------------------------------
