@@ -16,7 +16,8 @@
 
  - `AttentionPooling`: forward = esme_hip_attn_pool on the folded queries U, backward = esme_hip_attn_pool_bwd
    (include/esme_hip_attn_pool_bwd.h); `pool_fold` is the fold itself in fp32 torch ops, so that autograd carries dU on to the class
-   tokens and the key weight.  `SegmentMean`: forward = esme_hip_segment_mean, backward in torch ops.
+   tokens and the key weight.  `SegmentMean`: forward = esme_hip_segment_mean, backward =
+   esme_hip_segment_mean_bwd (include/esme_hip_segment_mean_bwd.h): no host read of cu_lens, so the node does not stall the stream.
 
 `forward_trainable` of the attention block, the layer and the model (esme/attention.py, esme/esm.py) is written with the first two and
 torch ops, in the reference's unfused data flow; `forward_trainable` of the task heads (esme/pooling.py, esme/head.py) with the pooling
@@ -29,7 +30,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_gemm_wgrad
+from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_gemm_wgrad, _hip_segment_mean_bwd
 from esme.nn import weight_t
 
 
@@ -188,8 +189,9 @@ def pool_fold(cls: torch.Tensor, k_weight: torch.Tensor, heads: int) -> torch.Te
 
 
 class SegmentMean(torch.autograd.Function):
-    """(B, E) per-sequence mean of the rows of x (T, E) bfloat16 / float32 (esme_hip_segment_mean); backward dY[seg] / len in torch
-    ops, in x's dtype."""
+    """(B, E) per-sequence mean of the rows of x (T, E) bfloat16 / float32 (esme_hip_segment_mean); backward dY[seg] / len
+    (fp32 division, one rounding to x's dtype; zero rows outside the sequences) on esme_hip_segment_mean_bwd, without a host
+    synchronisation."""
 
     @staticmethod
     def forward(ctx, x, cu_lens):
@@ -203,13 +205,9 @@ class SegmentMean(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         cu_lens, = ctx.saved_tensors
-        lens = (cu_lens[1:] - cu_lens[:-1]).to(torch.long)
-        g = (dy.float() / lens.clamp(min=1).view(-1, 1)).to(dy.dtype)
-        dx = torch.zeros(ctx.rows, dy.shape[1], dtype=dy.dtype, device=dy.device)
-        seg = torch.repeat_interleave(torch.arange(lens.numel(), device=dy.device), lens)
-        start = int(cu_lens[0])
-        dx[start:start + seg.numel()] = g[seg]
-        return dx, None
+        if dy.stride(1) != 1 or (dy.stride(0) * dy.element_size()) % 16 or dy.data_ptr() % 16:
+            dy = dy.contiguous()
+        return _hip_segment_mean_bwd.segment_mean_bwd(dy, cu_lens, ctx.rows), None
 
 
 def relu_mlp(x: torch.Tensor, lin, final) -> torch.Tensor:

@@ -5,7 +5,9 @@ The caller side of the hot path: `FastaTokenDataset[i]` is exactly the
 greedy packing rule follow `esme/data.py:12-60,63-162` of the reference.  `MaskedFastaDataset` /
 `MaskedFastaTokenDataset` add the masked-token corruption of `esme.alphabet.mask_tokens` for
 masked-LM training (the reference's constructor arguments and item layouts, data.py:165-245);
-the Lightning data modules (data.py:247-520) stay out of scope.
+`LabeledDataset` pairs in-memory sequences with one label each for supervised fine-tuning (esme.trainer.RegressionModel; the
+reference's constructor arguments and item dict, data.py:377-407); the Lightning data modules (data.py:247-374, 410-520:
+MaskedFastaDataModule, LabeledDataModule) stay out of scope.
 """
 from __future__ import annotations
 
@@ -149,3 +151,32 @@ class MaskedFastaTokenDataset(FastaTokenDataset):
         tokens, unpad_args = super().__getitem__(idx)
         masked, mask = mask_tokens(tokens, self.mask_freq, self.alter_freq, alphabet=self.alphabet)
         return tokens, unpad_args, masked, mask
+
+
+class LabeledDataset(Dataset):
+    """Item i = the i-th token-budget batch of in-memory sequences with one number each, as a dict: `token`, `cu_lens`, `max_len`,
+    `indices` (what tokenize_unpad returns for the batch's sequences) and `label`, a float32 tensor in batch order.  The batches are
+    TokenSizeBatchSampler's over the sequences' FULL lengths; `truncate_len` cuts what is tokenised to its first `truncate_len`
+    residues, not what is budgeted (so a truncated batch is below its budget, as in the reference)."""
+
+    def __init__(self, seqs, labels, token_per_batch, shuffle=True, random_state=None, truncate_len=None):
+        if len(seqs) != len(labels):
+            raise ValueError(f'LabeledDataset: {len(seqs)} sequences but {len(labels)} labels')
+        self.seqs, self.labels, self.truncate_len = seqs, labels, truncate_len
+        self.sampler = list(TokenSizeBatchSampler([len(s) for s in seqs], token_per_batch, shuffle=shuffle, random_state=random_state))
+
+    def truncate(self, seq):
+        return seq if self.truncate_len is None else seq[:self.truncate_len]
+
+    def __len__(self):
+        return len(self.sampler)
+
+    def __getitem__(self, idx):
+        batch = self.sampler[idx]
+        token, indices, cu_lens, max_len = tokenize_unpad([self.truncate(self.seqs[i]) for i in batch])
+        label = torch.tensor([float(self.labels[i]) for i in batch], dtype=torch.float32)
+        return {'token': token, 'cu_lens': cu_lens, 'max_len': max_len, 'indices': indices, 'label': label}
+
+    def to_dataloader(self, num_workers=0, **kwargs):
+        """One packed batch per item (batch_size=None); see FastaTokenDataset.to_dataloader on `num_workers`."""
+        return DataLoader(self, num_workers=num_workers, batch_size=None, **kwargs)

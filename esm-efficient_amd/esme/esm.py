@@ -784,7 +784,7 @@ class ESM2(nn.Module):
 
     # -- LoRA fine-tuning (esme/autograd.py) -------------------------------------------------------------------------
     def forward_trainable(self, tokens, pad_args=None, pad_output=False, pad_indices=None, lora_names=None, logits=True,
-                          checkpoint_layers=False):
+                          checkpoint_layers=False, layers=None):
         """model(...) with a grad_fn: logits (T, V) / (B, S, V), or with logits=False the final-LayerNorm representation, as a
         differentiable function of the adapters `lora_names` selects (None / empty: all), of the LM head where mark_lmhead(True)
         made it trainable, and of the layers' projections and LayerNorms where mark_trainable() did (full fine-tuning).  The
@@ -797,7 +797,12 @@ class ESM2(nn.Module):
         name, for a precision other than 'fast', quantised weights (unless add_lora(quantized_base=True) opted in: then the adapters
         and the LM head train over the quantised base, and a LayerNorm that requires grad is refused), the padded ESM2-35M layout, dropout > 0, a head dim outside
         {32, 64}, the learned-position ESM-1 models and a token embedding that requires grad without mark_trainable(embedding=True)
-        (with it the table trains: esme.autograd.TokenEmbedding; quantised models stay refused)."""
+        (with it the table trains: esme.autograd.TokenEmbedding; quantised models stay refused).
+        `layers=[...]` (with logits=False; ValueError with logits=True, the LM head takes E columns) taps the raw outputs of those
+        layers as forward_representation(layers=) does -- the same check of the indices, the same order (that of the model's layers)
+        -- and concatenates them after the final-LayerNorm output on the feature axis: (T, (1 + k) E) / (B, S, (1 + k) E), every
+        column block with a grad_fn, so that a head of width (1 + k) E trains the backbone through the taps (the reference's
+        RegressionTrainer(layers=...)).  The taps are the tensors the next layer reads, not copies; None / empty changes nothing."""
         from esme import autograd as ag
         train_emb = bool(self.__dict__.get('_train_embedding', False))
         ag.refuse(self.embed_tokens.weight.requires_grad and not train_emb,
@@ -820,6 +825,12 @@ class ESM2(nn.Module):
                 if n not in have:
                     raise KeyError(f'LoRA adapter {n!r} not found (available: {have})')
         names = tuple(lora_names) if lora_names else None
+        tap_at = list(layers) if layers else []
+        self._check_layers_arg(tap_at)
+        if tap_at and logits:
+            raise ValueError(f'forward_trainable: layers={tap_at} needs logits=False (the LM head takes the {self.embed_dim} columns of the '
+                             'final-LayerNorm output, not the concatenation with the tapped layers)')
+        taps = []
         with _hip.stream_scope(self.embed_tokens.weight.device):
             if pad_args is not None:
                 assert tokens.ndim == 1, 'tokens are expected to be unpadded with shape (batch * seq_len)'
@@ -846,15 +857,21 @@ class ESM2(nn.Module):
                 cu_lens = cu_lens.to(torch.int32)
             max_len = int(max_len)
             pos, _ = _hip.seq_positions(cu_lens, x.shape[0])
-            for layer in self.layers:
+            for i, layer in enumerate(self.layers):
                 if checkpoint_layers:
                     from torch.utils.checkpoint import checkpoint
                     x = checkpoint(layer.forward_trainable, x, cu_lens, max_len, names, pos, use_reentrant=False)
                 else:
                     x = layer.forward_trainable(x, cu_lens, max_len, names, pos)
+                if i in tap_at:
+                    taps.append(x)
             x = ag.layer_norm(x, self.emb_layer_norm_after)
             if pad_output or pad_args is None:                    # (before the head, as in forward(): pad rows hold head(0))
-                x = ag.pad_rows(x, pad_indices, cu_lens.numel() - 1, tokens.shape[1] if pad_args is None else max_len)
+                width = tokens.shape[1] if pad_args is None else max_len
+                x = ag.pad_rows(x, pad_indices, cu_lens.numel() - 1, width)
+                taps = [ag.pad_rows(t, pad_indices, cu_lens.numel() - 1, width) for t in taps]
+            if taps:
+                return torch.cat((x, *taps), dim=-1)
             return self.lm_head.forward_trainable(x) if logits else x
 
     def mark_lmhead(self, trainable=True):
