@@ -3,8 +3,9 @@
 // Per sequence (S rows) and listed head j (head h = head_list[j]):  P = softmax_j(q_i . k_j * scale) over all S keys, stored.
 // Two launches per call, each a sweep of 64 x 64 score tiles on v_mfma_f32_16x16x32_bf16 (score_tiles.h: fp32 accumulators,
 // softmax in fp32 log2 units):
-//  - attn_map_stats_kernel  per (sequence, listed head, 64 query rows): all key tiles twice -> the exact row maximum m and the
-//                           row sum l of exp2(s - m), into the workspace (the statistics pass of contacts.hip without a trim);
+//  - attn_map_stats_kernel  per (sequence, listed head, 64 query rows): softmax_row_stats of score_tiles.h (all key tiles twice -> the
+//                           exact row maximum m and the row sum l of exp2(s - m); contact_stats_kernel runs the same pass with its
+//                           trim), stored into the workspace;
 //  - attn_map_write_kernel  per (sequence, block, 64 query rows x 64 keys): the tile's scores again, P = exp2(s - m) * (1 / l),
 //                           stored from the accumulator layout (a lane holds rows 4 g .. 4 g + 3 of column c: 16 lanes write a
 //                           64-byte run of one row in fp32).  Weighted mode: the listed heads in list order,
@@ -33,7 +34,6 @@ struct MapArgs {
 
 template <int D>
 __global__ __launch_bounds__(256) void attn_map_stats_kernel(const MapArgs a) {
-    constexpr int DS = TileDims<D>::DS;
     __shared__ __attribute__((aligned(16))) u16 tile[kCT * TileDims<D>::LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
     const int b = a.b0 + blockIdx.z, j = blockIdx.y, h = a.heads[j];
@@ -45,51 +45,15 @@ __global__ __launch_bounds__(256) void attn_map_stats_kernel(const MapArgs a) {
     const u16* kb = a.k + (int64_t)s0 * a.ld + h * D;
     int qi = I0 + wave * 16 + c;
     qi = qi < S ? qi : S - 1;
-    bf16x8 af[DS];
-#pragma unroll
-    for (int ks = 0; ks < DS; ++ks) af[ks] = global_frag<D>(qb, ld, qi, ks, g);
-
-    f32x4 s[4];
-    float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int kt = 0; kt < S; kt += kCT) {
-        __syncthreads();
-        stage_tile<D>(tile, kb, ld, kt, S);
-        __syncthreads();
-        score_tile<D>(af, tile, c, g, s);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            if (kt + cb * 16 + c < S) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], s[cb][r] * a.cs);                    // [score-scale]
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = row16_max(mx[r]);
-
-    float ls[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < S; kt += kCT) {
-        __syncthreads();
-        stage_tile<D>(tile, kb, ld, kt, S);
-        __syncthreads();
-        score_tile<D>(af, tile, c, g, s);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const bool live = kt + cb * 16 + c < S;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ls[r] += live ? exp2f(s[cb][r] * a.cs - mx[r]) : 0.f;        // [exp] [row-sum]
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ls[r] = row16_sum(ls[r]);
+    const RowStats st = softmax_row_stats<D, false>(tile, qb, kb, ld, qi, S, a.cs, 0, 0, c, g);
     if (c == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = I0 + wave * 16 + 4 * g + r;
             if (row < S) {
                 const int64_t idx = (int64_t)j * a.T + s0 + row;
-                a.ws_m[idx] = mx[r];
-                a.ws_l[idx] = ls[r];
+                a.ws_m[idx] = st.m[r];
+                a.ws_l[idx] = st.l[r];
             }
         }
     }
@@ -202,29 +166,21 @@ extern "C" int esme_hip_attn_maps(const void* q, const void* k, int64_t ld_qk, c
                                   void* workspace, int64_t ws_bytes, void* stream) {
     ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0 && n_heads > 0 && slot0 >= 0, "attn_maps: bad sizes");
     if (B == 0 || T == 0) return ESME_OK;
-    ESME_CHECK_ARG(q && k && cu_lens && head_list && map && map_off && workspace, "attn_maps: null pointer");
-    ESME_CHECK_ARG(ld_qk % 8 == 0 && ld_qk >= (int64_t)H * d, "attn_maps: bad row stride");
-    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(workspace) && (reinterpret_cast<uintptr_t>(map) & (out_bf16 ? 1u : 3u)) == 0 &&
-                   (reinterpret_cast<uintptr_t>(head_list) & 3u) == 0 && (reinterpret_cast<uintptr_t>(head_weights) & 3u) == 0 &&
-                   (reinterpret_cast<uintptr_t>(map_off) & 7u) == 0, "attn_maps: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && n_heads <= 65535 && T < 0x80000000LL,
-                   "attn_maps: max_len must be > 0, H <= 65535, n_heads <= 65535, T < 2^31");
-    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_maps: head dim must be 16, 32, 64 or 128");
-    if ((int64_t)max_len * ld_qk >= ESME_HIP_CONTACT_MAX_SEQ_ELEMS)
-        ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_maps: max_len * ld_qk passes 2^32 elements (ESME_HIP_CONTACT_MAX_SEQ_ELEMS)");
+    float cs;
+    const QKEntryChecks own{head_list && map && map_off, nullptr,
+                            (reinterpret_cast<uintptr_t>(map) & (out_bf16 ? 1u : 3u)) == 0 && (reinterpret_cast<uintptr_t>(head_list) & 3u) == 0 &&
+                                (reinterpret_cast<uintptr_t>(head_weights) & 3u) == 0 && (reinterpret_cast<uintptr_t>(map_off) & 7u) == 0,
+                            n_heads <= 65535, "attn_maps: max_len must be > 0, H <= 65535, n_heads <= 65535, T < 2^31"};
+    if (const int rc = check_qk_operands("attn_maps", q, k, ld_qk, cu_lens, T, H, d, max_len, softmax_scale, q_prescaled, workspace, own, &cs))
+        return rc;
     const int64_t need = esme_hip_attn_maps_workspace_bytes(B, T, n_heads);
     ESME_CHECK_ARG(ws_bytes >= need, "attn_maps: workspace too small (see esme_hip_attn_maps_workspace_bytes)");
     const int64_t nt = ((int64_t)max_len + kCT - 1) / kCT;
     if (nt * nt > 0x7fffffffLL) ESME_FAIL(ESME_ERR_UNSUPPORTED, "attn_maps: too many tiles");
     float* ws = (float*)workspace;
-    const MapArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, T, q_prescaled ? 1.0f : softmax_scale * 1.4426950408889634f,
+    const MapArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, T, cs,
                     head_list, n_heads, head_weights, ws, ws + (int64_t)n_heads * T, map, map_off, slot0, (int)nt};
-    const hipStream_t s = (hipStream_t)stream;
-    const bool bf16 = out_bf16 != 0;
-    switch (d) {
-        case 16: return launch_maps<16>(a, B, bf16, s);
-        case 32: return launch_maps<32>(a, B, bf16, s);
-        case 64: return launch_maps<64>(a, B, bf16, s);
-        default: return launch_maps<128>(a, B, bf16, s);
-    }
+    return dispatch_head_dim<16, 32, 64, 128>(d, "attn_maps: head dim must be 16, 32, 64 or 128", [&](auto D) {
+        return launch_maps<D()>(a, B, out_bf16 != 0, (hipStream_t)stream);
+    });
 }

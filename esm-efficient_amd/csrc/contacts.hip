@@ -5,15 +5,17 @@
 //     map += sum_h w_h (Y - r r^T / t).
 // Everything but r r^T / t is linear in P, so no S x S object is ever stored: four launches per layer, each a sweep of
 // 64 x 64 score tiles on v_mfma_f32_16x16x32_bf16 (fp32 accumulators, softmax in fp32 log2 units, P never rounded):
-//  - contact_stats_kernel   per (sequence, head, 64 query rows): all key tiles twice -> row maximum m, row sum l, and the
-//                           row sum of A (the sum over the kept keys only, times 1 / l);
+//  - contact_stats_kernel   per (sequence, head, 64 query rows): all key tiles twice (softmax_row_stats of score_tiles.h, the pass
+//                           attn_maps.hip runs without a trim) -> row maximum m, row sum l, and the row sum of A (the sum over the
+//                           kept keys only, times 1 / l);
 //  - contact_colsum_kernel  per (sequence, head, 64 key rows): all kept query tiles, P normalised with their m, l -> column sums
 //                           of A; r = row sum + column sum;
 //  - contact_total_kernel   per (sequence, head): t = sum_i r_i, lane-strided partial sums and one butterfly (a fixed order);
 //  - contact_pair_kernel    per (sequence, tile pair I <= J), heads in index order: S_IJ = Q_I K_J^T and S_JI^T = K_I Q_J^T land in
 //                           the same register layout, acc += w_h (A_IJ + A_JI^T) - (w_h / t_h) r_I r_J^T; the tile and its mirror
 //                           image are stored (or added to the map) from the same registers: the map is exactly symmetric.
-// The tile code (operand fragments, LDS staging, the score MFMAs) is score_tiles.h, shared with the attention backward.
+// The tile code (operand fragments, LDS staging, the score MFMAs) is score_tiles.h, shared with the attention backward; the checks
+// of the (q, k) operand arguments (check_qk_operands) are there too, shared with esme_hip_attn_maps.
 // Every index is relative to the sequence's own first row and every reduction has a fixed order: a sequence's map does not
 // depend on its neighbours (bit-identical alone and packed, run to run).  No atomics.
 //
@@ -42,7 +44,6 @@ struct ContactArgs {
 
 template <int D>
 __global__ __launch_bounds__(256) void contact_stats_kernel(const ContactArgs a) {
-    constexpr int DS = TileDims<D>::DS;
     __shared__ __attribute__((aligned(16))) u16 tile[kCT * TileDims<D>::LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
     const int b = a.b0 + blockIdx.z, h = blockIdx.y;
@@ -54,60 +55,16 @@ __global__ __launch_bounds__(256) void contact_stats_kernel(const ContactArgs a)
     const u16* kb = a.k + (int64_t)s0 * a.ld + h * D;
     int qi = I0 + wave * 16 + c;
     qi = qi < n ? qi : n - 1;
-    bf16x8 af[DS];
-#pragma unroll
-    for (int ks = 0; ks < DS; ++ks) af[ks] = global_frag<D>(qb, ld, a.f + qi, ks, g);
-
-    f32x4 s[4];
-    float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int kt = 0; kt < S; kt += kCT) {
-        __syncthreads();
-        stage_tile<D>(tile, kb, ld, kt, S);
-        __syncthreads();
-        score_tile<D>(af, tile, c, g, s);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            if (kt + cb * 16 + c < S) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], s[cb][r] * a.cs);                    // [score-scale]
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = row16_max(mx[r]);
-
-    float ls[4] = {0.f, 0.f, 0.f, 0.f}, lt[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < S; kt += kCT) {
-        __syncthreads();
-        stage_tile<D>(tile, kb, ld, kt, S);
-        __syncthreads();
-        score_tile<D>(af, tile, c, g, s);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const int key = kt + cb * 16 + c;
-            const bool kept = key >= a.f && key < S - a.e;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = key < S ? exp2f(s[cb][r] * a.cs - mx[r]) : 0.f;                       // [exp]
-                ls[r] += p;                                                                           // [row-sum]
-                lt[r] += kept ? p : 0.f;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        ls[r] = row16_sum(ls[r]);
-        lt[r] = row16_sum(lt[r]);
-    }
+    const RowStats st = softmax_row_stats<D, true>(tile, qb, kb, ld, a.f + qi, S, a.cs, a.f, a.e, c, g);
     if (c == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = I0 + wave * 16 + 4 * g + r;
             if (row < n) {
                 const int64_t idx = (int64_t)h * a.T + s0 + a.f + row;
-                a.ws_m[idx] = mx[r];
-                a.ws_l[idx] = ls[r];
-                a.ws_r[idx] = lt[r] * (1.0f / ls[r]);                                                 // [inv-l] [normalise]
+                a.ws_m[idx] = st.m[r];
+                a.ws_l[idx] = st.l[r];
+                a.ws_r[idx] = st.lt[r] * (1.0f / st.l[r]);                                                 // [inv-l] [normalise]
             }
         }
     }
@@ -265,15 +222,21 @@ __global__ __launch_bounds__(256) void contact_pair_kernel(const ContactArgs a) 
     }
 }
 
+// m, l, r and t of sequences a.b0 .. a.b0 + nb - 1 into the workspace: the three statistics launches
+template <int D>
+static void launch_contact_stats(const ContactArgs& a, int nt, int nb, hipStream_t s) {
+    const dim3 tiles((unsigned int)nt, (unsigned int)a.H, (unsigned int)nb);
+    hipLaunchKernelGGL(contact_stats_kernel<D>, tiles, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(contact_colsum_kernel<D>, tiles, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(contact_total_kernel, dim3((unsigned int)a.H, (unsigned int)nb), dim3(64), 0, s, a);
+}
+
 template <int D>
 static int launch_contacts(const ContactArgs& a0, int nt, int64_t npairs, hipStream_t s) {
     return for_sequence_chunks(a0.B, kContactMaxZ, [&](int b0, int nb) {
         ContactArgs a = a0;
         a.b0 = b0;
-        const dim3 tiles((unsigned int)nt, (unsigned int)a.H, (unsigned int)nb);
-        hipLaunchKernelGGL(contact_stats_kernel<D>, tiles, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(contact_colsum_kernel<D>, tiles, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(contact_total_kernel, dim3((unsigned int)a.H, (unsigned int)nb), dim3(64), 0, s, a);
+        launch_contact_stats<D>(a, nt, nb, s);
         hipLaunchKernelGGL(contact_pair_kernel<D>, dim3((unsigned int)npairs, 1u, (unsigned int)nb), dim3(256), 0, s, a);
         return check_launch("contact_layer");
     });
@@ -356,10 +319,7 @@ static int launch_features(const ContactArgs& a0, const GatherArgs& ga, int nt, 
         const int rc = for_sequence_chunks(a0.B, kContactMaxZ, [&](int b0, int nb) {
             ContactArgs a = a0;
             a.b0 = b0;
-            const dim3 tiles((unsigned int)nt, (unsigned int)a.H, (unsigned int)nb);
-            hipLaunchKernelGGL(contact_stats_kernel<D>, tiles, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(contact_colsum_kernel<D>, tiles, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(contact_total_kernel, dim3((unsigned int)a.H, (unsigned int)nb), dim3(64), 0, s, a);
+            launch_contact_stats<D>(a, nt, nb, s);
             return check_launch("contact_features");
         });
         if (rc) return rc;
@@ -383,13 +343,11 @@ extern "C" int esme_hip_contact_layer(const void* q, const void* k, int64_t ld_q
                                       int64_t ws_bytes, void* stream) {
     ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0 && trim_front >= 0 && trim_back >= 0, "contact_layer: bad sizes");
     if (B == 0 || T == 0) return ESME_OK;
-    ESME_CHECK_ARG(q && k && cu_lens && w && map && map_off && workspace, "contact_layer: null pointer");
-    ESME_CHECK_ARG(ld_qk % 8 == 0 && ld_qk >= (int64_t)H * d, "contact_layer: bad row stride");
-    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(workspace) && (reinterpret_cast<uintptr_t>(map) & 3u) == 0, "contact_layer: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && T < 0x80000000LL, "contact_layer: max_len must be > 0, H <= 65535, T < 2^31");
-    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_layer: head dim must be 16, 32, 64 or 128");
-    if ((int64_t)max_len * ld_qk >= ESME_HIP_CONTACT_MAX_SEQ_ELEMS)
-        ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_layer: max_len * ld_qk passes 2^32 elements (ESME_HIP_CONTACT_MAX_SEQ_ELEMS)");
+    float cs;
+    const QKEntryChecks own{w && map && map_off, nullptr, (reinterpret_cast<uintptr_t>(map) & 3u) == 0, true,
+                            "contact_layer: max_len must be > 0, H <= 65535, T < 2^31"};
+    if (const int rc = check_qk_operands("contact_layer", q, k, ld_qk, cu_lens, T, H, d, max_len, softmax_scale, q_prescaled, workspace, own, &cs))
+        return rc;
     const int64_t need = esme_hip_contact_workspace_bytes(B, T, H);
     ESME_CHECK_ARG(ws_bytes >= need, "contact_layer: workspace too small (see esme_hip_contact_workspace_bytes)");
     const int64_t nmax = (int64_t)max_len - trim_front - trim_back;
@@ -398,16 +356,11 @@ extern "C" int esme_hip_contact_layer(const void* q, const void* k, int64_t ld_q
     if (npairs > 0x7fffffffLL) ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_layer: too many tile pairs");
     float* ws = (float*)workspace;
     const int64_t HT = (int64_t)H * T;
-    ContactArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, B, T, H,
-                  q_prescaled ? 1.0f : softmax_scale * 1.4426950408889634f, trim_front, trim_back,
+    ContactArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, B, T, H, cs, trim_front, trim_back,
                   ws, ws + HT, ws + 2 * HT, ws + 3 * HT, w, bias, init, map, map_off};
-    const hipStream_t s = (hipStream_t)stream;
-    switch (d) {
-        case 16: return launch_contacts<16>(a, (int)nt, npairs, s);
-        case 32: return launch_contacts<32>(a, (int)nt, npairs, s);
-        case 64: return launch_contacts<64>(a, (int)nt, npairs, s);
-        default: return launch_contacts<128>(a, (int)nt, npairs, s);
-    }
+    return dispatch_head_dim<16, 32, 64, 128>(d, "contact_layer: head dim must be 16, 32, 64 or 128", [&](auto D) {
+        return launch_contacts<D()>(a, (int)nt, npairs, (hipStream_t)stream);
+    });
 }
 
 extern "C" int64_t esme_hip_contact_features_workspace_bytes(int B, int64_t T, int H) {
@@ -422,16 +375,12 @@ extern "C" int esme_hip_contact_features(const void* q, const void* k, int64_t l
     ESME_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && d > 0 && max_len >= 0 && trim_front >= 0 && trim_back >= 0 && P >= 0 && col0 >= 0,
                    "contact_features: bad sizes");
     if (B == 0 || T == 0 || P == 0) return ESME_OK;
-    ESME_CHECK_ARG(q && k && cu_lens && pairs && feat && workspace, "contact_features: null pointer");
-    ESME_CHECK_ARG(ld_qk % 8 == 0 && ld_qk >= (int64_t)H * d, "contact_features: bad row stride");
-    ESME_CHECK_ARG(ld_feat >= (int64_t)col0 + H, "contact_features: ld_feat must be at least col0 + H");
-    ESME_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(workspace) && (reinterpret_cast<uintptr_t>(feat) & 3u) == 0 &&
-                   (reinterpret_cast<uintptr_t>(pairs) & 3u) == 0, "contact_features: misaligned");
-    ESME_CHECK_ARG(max_len > 0 && H <= 65535 && T < 0x80000000LL && P < 0x80000000LL,
-                   "contact_features: max_len must be > 0, H <= 65535, T < 2^31, P < 2^31");
-    if (d != 16 && d != 32 && d != 64 && d != 128) ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_features: head dim must be 16, 32, 64 or 128");
-    if ((int64_t)max_len * ld_qk >= ESME_HIP_CONTACT_MAX_SEQ_ELEMS)
-        ESME_FAIL(ESME_ERR_UNSUPPORTED, "contact_features: max_len * ld_qk passes 2^32 elements (ESME_HIP_CONTACT_MAX_SEQ_ELEMS)");
+    float cs;
+    const QKEntryChecks own{pairs && feat, ld_feat >= (int64_t)col0 + H ? nullptr : "contact_features: ld_feat must be at least col0 + H",
+                            (reinterpret_cast<uintptr_t>(feat) & 3u) == 0 && (reinterpret_cast<uintptr_t>(pairs) & 3u) == 0, P < 0x80000000LL,
+                            "contact_features: max_len must be > 0, H <= 65535, T < 2^31, P < 2^31"};
+    if (const int rc = check_qk_operands("contact_features", q, k, ld_qk, cu_lens, T, H, d, max_len, softmax_scale, q_prescaled, workspace, own, &cs))
+        return rc;
     const int64_t need = esme_hip_contact_features_workspace_bytes(B, T, H);
     ESME_CHECK_ARG(ws_bytes >= need, "contact_features: workspace too small (see esme_hip_contact_features_workspace_bytes)");
     int64_t nmax = (int64_t)max_len - trim_front - trim_back;
@@ -439,15 +388,10 @@ extern "C" int esme_hip_contact_features(const void* q, const void* k, int64_t l
     const int64_t nt = (nmax + kCT - 1) / kCT;
     float* ws = (float*)workspace;
     const int64_t HT = (int64_t)H * T;
-    ContactArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, B, T, H,
-                  q_prescaled ? 1.0f : softmax_scale * 1.4426950408889634f, trim_front, trim_back,
+    ContactArgs a{(const u16*)q, (const u16*)k, ld_qk, cu_lens, 0, B, T, H, cs, trim_front, trim_back,
                   ws, ws + HT, ws + 2 * HT, ws + 3 * HT, nullptr, 0.f, 0, nullptr, nullptr};
     const GatherArgs ga{pairs, P, feat, ld_feat, col0, (int)nmax};
-    const hipStream_t s = (hipStream_t)stream;
-    switch (d) {
-        case 16: return launch_features<16>(a, ga, (int)nt, s);
-        case 32: return launch_features<32>(a, ga, (int)nt, s);
-        case 64: return launch_features<64>(a, ga, (int)nt, s);
-        default: return launch_features<128>(a, ga, (int)nt, s);
-    }
+    return dispatch_head_dim<16, 32, 64, 128>(d, "contact_features: head dim must be 16, 32, 64 or 128", [&](auto D) {
+        return launch_features<D()>(a, ga, (int)nt, (hipStream_t)stream);
+    });
 }

@@ -10,7 +10,7 @@ from typing import Optional
 
 import torch
 
-from esme import _hip
+from esme import _hip, _hip_contacts
 
 SIGNATURES = {
     'esme_hip_attn_maps_workspace_bytes': (c_int64, [c_int, c_int64, c_int]),
@@ -43,10 +43,7 @@ def workspace_bytes(B: int, T: int, n_heads: int) -> int:
 def map_offsets(cu_lens: torch.Tensor, blocks: int = 1):
     """(S (B) int64, map_off (B) int64, total) on cu_lens' device: sequence s owns `blocks` row-major S_s x S_s blocks, blocks * S_s^2
     elements at map_off[s] (block i at map_off[s] + i * S_s^2); an empty sequence owns nothing."""
-    S = (cu_lens[1:] - cu_lens[:-1]).to(torch.int64).clamp_(min=0)
-    sq = S * S * int(blocks)
-    off = torch.cumsum(sq, 0) - sq
-    return S, off, int(sq.sum())
+    return _hip_contacts.map_offsets(cu_lens, 0, 0, blocks)
 
 
 def attn_maps(q: torch.Tensor, k: torch.Tensor, cu_lens: torch.Tensor, max_len: int, heads: int, head_dim: int, softmax_scale: float,

@@ -40,11 +40,12 @@ def workspace_bytes(B: int, T: int, H: int) -> int:
     return int(n)
 
 
-def map_offsets(cu_lens: torch.Tensor, trim_front: int, trim_back: int):
-    """(n (B) int64, map_off (B) int64, total) on cu_lens' device: sequence s owns n_s x n_s floats at map_off[s]."""
+def map_offsets(cu_lens: torch.Tensor, trim_front: int, trim_back: int, blocks: int = 1):
+    """(n (B) int64, map_off (B) int64, total) on cu_lens' device: sequence s owns `blocks` row-major n_s x n_s blocks at map_off[s]
+    (block i at map_off[s] + i * n_s^2), n_s = its length without the trimmed rows; a sequence trimmed to nothing owns nothing."""
     lens = (cu_lens[1:] - cu_lens[:-1]).to(torch.int64)
     n = (lens - (trim_front + trim_back)).clamp_(min=0)
-    sq = n * n
+    sq = n * n * int(blocks)
     off = torch.cumsum(sq, 0) - sq
     return n, off, int(sq.sum())
 

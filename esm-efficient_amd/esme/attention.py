@@ -48,7 +48,7 @@ def _q_scale(head_dim: int) -> float:
 class ForwardContext:
     """Per-forward shared state: row positions, rotary tables (computed once, not per
     layer) and the LayerNorm-statistics plumbing of the fused path."""
-    __slots__ = ('pos', 'cos', 'sin', 'sums', 'part_a', 'part_b', 'fold', 'exact_attn', 'x32', 'order', 'scratch', 'f16', 'xs', 'plan', 'probe', 'ovf', 'cos32', 'sin32', 'guard', 'lora_x', 'contacts',
+    __slots__ = ('pos', 'cos', 'sin', 'sums', 'part_a', 'part_b', 'fold', 'exact_attn', 'x32', 'order', 'scratch', 'f16', 'xs', 'plan', 'probe', 'ovf', 'cos32', 'sin32', 'guard', 'lora_x', 'observer',
                  'sites', 'fast_site')
 
     def __init__(self, pos, cos, sin, fold=False, exact_attn=False, f16=False, plan=None, cos32=None, sin32=None, probe=None, ovf=None, guard=None):
@@ -68,7 +68,7 @@ class ForwardContext:
         self.sums = None            # partial sums (nblk, T, 2) f32 describing the current residual stream
         self.part_a = None          # (stats_blocks, T, 2) f32 buffers the residual GEMMs write their row sums to
         self.part_b = None
-        self.contacts = None        # predict_contacts: esme.contacts.ContactAccumulator -- every attention block hands it its final (q, k)
+        self.observer = None        # predict_contacts / contact_features / attention_maps: an esme.qk_observer.QKObserver -- every attention block hands it its final (q, k)
         self.lora_x = None          # LoRA: the (T, E + X) buffer whose first E columns ARE the residual stream; the last X hold the QKV adapters' down-projection
         self.sites = None           # 'high' / 'half': per residual epilogue (layer i attention: 2 i, FFN: 2 i + 1) the keyword arguments that name the stream
         self.fast_site = None       # 'fast': the same for the bf16 stream (one dict while the layers run in place)
@@ -561,8 +561,8 @@ class FlashMultiheadAttention(nn.Module):
                     q, k = self.rot_emb(q, k, cu_lens, max_len, inplace=True)
         if ctx is not None and ctx.probe is not None:
             ctx.probe.append(_score_bound(q.reshape(T, E), k.reshape(T, E), H, d, self.head_dim ** -0.5))
-        if ctx is not None and ctx.contacts is not None:        # q and k are final here (rotated, ESM-C: normalised; `qp`: q carries the softmax scale)
-            ctx.contacts.layer(self.layer_index, q, k, qp)
+        if ctx is not None and ctx.observer is not None:        # q and k are final here (rotated, ESM-C: normalised; `qp`: q carries the softmax scale)
+            ctx.observer.layer(self.layer_index, q, k, qp)
         a, wo, bo = self._out_operands(lw, f16, q, k, v, cu_lens, max_len, exact=bool(ctx is not None and ctx.exact_attn),
                                        order=ctx.order if ctx is not None else None, q_prescaled=qp)
         if stream is not None:

@@ -16,6 +16,7 @@ from typing import Optional, Sequence
 import torch
 
 from esme import _hip_attn_maps
+from esme.qk_observer import QKObserver
 
 DTYPES = (torch.float32, torch.bfloat16)
 
@@ -63,17 +64,16 @@ def buffer_bytes(lengths: Sequence[int], n_layers: int, n_out: int, dtype: torch
     return n_layers * n_out * sum(int(s) * int(s) for s in lengths) * torch.empty(0, dtype=dtype).element_size()
 
 
-class AttentionMapAccumulator:
-    """What ForwardContext.contacts holds during attention_maps: the same `.layer(index, q, k, q_prescaled)` hook as ContactAccumulator.
-    Unselected layers are ignored; the i-th selected layer's maps go to slots i * n_out .. of every protein's block run
-    (esme_hip_attn_maps; n_out = len(heads), or 1 with head weights).  layers / heads: validated index lists; weights: None or float32
-    (len(layers), len(heads)).  `keep_qk` (tests): clones of each layer's (layer, q, k, q_prescaled) in `.qk`."""
+class AttentionMapAccumulator(QKObserver):
+    """The observer of attention_maps.  Unselected layers are turned away; the i-th selected layer's maps go to slots i * n_out .. of
+    every protein's block run (esme_hip_attn_maps; n_out = len(heads), or 1 with head weights).  layers / heads: validated index lists;
+    weights: None or float32 (len(layers), len(heads))."""
 
     def __init__(self, layers, heads, weights: Optional[torch.Tensor], dtype: torch.dtype, cu_lens: torch.Tensor, max_len: int,
                  model_heads: int, head_pad: int, head_dim: int, keep_qk: bool = False):
+        super().__init__(cu_lens, max_len, model_heads, head_pad, head_dim,
+                         lambda B, T: _hip_attn_maps.workspace_bytes(B, T, len(heads)), keep_qk)
         dev = cu_lens.device
-        self.cu_lens, self.max_len, self.heads, self.head_pad = cu_lens, int(max_len), int(model_heads), int(head_pad)
-        self.scale = float(head_dim) ** -0.5                     # of the LOGICAL head dim (a padded layout's pad lanes are zero)
         self.layers, self.sel = list(layers), list(heads)
         self.slot = {l: i for i, l in enumerate(self.layers)}
         self.head_list = torch.tensor(self.sel, dtype=torch.int32, device=dev)
@@ -81,29 +81,16 @@ class AttentionMapAccumulator:
         self.n_out = 1 if weights is not None else len(self.sel)
         self.S, self.map_off, total = _hip_attn_maps.map_offsets(cu_lens, len(self.layers) * self.n_out)
         self.out = torch.empty(total, dtype=dtype, device=dev)
-        B, T = cu_lens.numel() - 1, int(cu_lens[-1])
-        self.ws = torch.empty(max(_hip_attn_maps.workspace_bytes(B, T, len(self.sel)), 16), dtype=torch.uint8, device=dev)
-        self.done = []
-        self.qk = [] if keep_qk else None
 
-    def layer(self, index: int, q: torch.Tensor, k: torch.Tensor, q_prescaled: bool) -> None:
-        if index not in self.slot and self.qk is None:
-            return
-        T = q.shape[0]
-        E = self.heads * self.head_pad
-        q2, k2 = (t.view(T, E) if t.dim() == 3 else t for t in (q, k))
-        if q2.stride(0) != k2.stride(0) or q2.stride(1) != 1 or k2.stride(1) != 1:
-            q2, k2 = q2.contiguous(), k2.contiguous()
-        if self.qk is not None:
-            self.qk.append((index, q2.clone(), k2.clone(), bool(q_prescaled)))
-        if index not in self.slot:
-            return
+    def wants(self, index: int) -> bool:
+        return index in self.slot
+
+    def launch(self, index: int, q2: torch.Tensor, k2: torch.Tensor, q_prescaled: bool) -> None:
         i = self.slot[index]
         if self.out.numel():
             _hip_attn_maps.attn_maps(q2, k2, self.cu_lens, self.max_len, self.heads, self.head_pad, self.scale, self.head_list, self.out,
                                      self.map_off, i * self.n_out, self.ws, head_weights=None if self.weights is None else self.weights[i],
                                      q_prescaled=q_prescaled)
-        self.done.append(index)
 
     def result(self):
         """List of B views of the one buffer: (L_sel, H_sel, S_b, S_b), with head weights (L_sel, S_b, S_b)."""

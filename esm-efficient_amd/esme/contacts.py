@@ -22,7 +22,8 @@ from typing import Optional
 import torch
 from torch import nn
 
-from esme import _hip, _hip_contact_features, _hip_contacts
+from esme import _hip_contact_features, _hip_contacts
+from esme.qk_observer import QKObserver
 
 
 class ContactHead(nn.Module):
@@ -194,37 +195,23 @@ class ContactHead(nn.Module):
         return head
 
 
-class ContactAccumulator:
-    """What ForwardContext.contacts holds during predict_contacts: every attention block hands it its final (q, k) and it adds that
-    layer's share to the packed logit map.  `keep_qk` (tests): clones of each layer's (layer, q, k, q_prescaled) in `.qk`."""
+class ContactAccumulator(QKObserver):
+    """The observer of predict_contacts: adds every layer's share to the packed logit map (esme_hip_contact_layer)."""
 
     def __init__(self, head: ContactHead, cu_lens: torch.Tensor, max_len: int, heads: int, head_pad: int, head_dim: int, keep_qk: bool = False):
+        super().__init__(cu_lens, max_len, heads, head_pad, head_dim, lambda B, T: _hip_contacts.workspace_bytes(B, T, heads), keep_qk)
         dev = cu_lens.device
-        self.cu_lens, self.max_len, self.heads, self.head_pad = cu_lens, int(max_len), int(heads), int(head_pad)
-        self.scale = float(head_dim) ** -0.5                     # of the LOGICAL head dim (a padded layout's pad lanes are zero)
         self.front, self.back = head.trim
         self.w = head.regression.weight.detach().to(device=dev, dtype=torch.float32).reshape(head.num_layers, heads).contiguous()
         self.bias = float(head.regression.bias.detach().float().reshape(-1)[0])
         self.n, self.map_off, total = _hip_contacts.map_offsets(cu_lens, self.front, self.back)
         self.out = torch.empty(total, dtype=torch.float32, device=dev)
-        B, T = cu_lens.numel() - 1, int(cu_lens[-1])
-        self.ws = torch.empty(max(_hip_contacts.workspace_bytes(B, T, heads), 16), dtype=torch.uint8, device=dev)
-        self.done = []
-        self.qk = [] if keep_qk else None
 
-    def layer(self, index: int, q: torch.Tensor, k: torch.Tensor, q_prescaled: bool) -> None:
-        T = q.shape[0]
-        E = self.heads * self.head_pad
-        q2, k2 = (t.view(T, E) if t.dim() == 3 else t for t in (q, k))
-        if q2.stride(0) != k2.stride(0) or q2.stride(1) != 1 or k2.stride(1) != 1:
-            q2, k2 = q2.contiguous(), k2.contiguous()
-        if self.qk is not None:
-            self.qk.append((index, q2.clone(), k2.clone(), bool(q_prescaled)))
+    def launch(self, index: int, q2: torch.Tensor, k2: torch.Tensor, q_prescaled: bool) -> None:
         if self.out.numel():
             _hip_contacts.contact_layer(q2, k2, self.cu_lens, self.max_len, self.heads, self.head_pad, self.scale, self.w[index], self.bias,
                                         not self.done, self.out, self.map_off, self.ws, q_prescaled=q_prescaled,
                                         trim_front=self.front, trim_back=self.back)
-        self.done.append(index)
 
     def result(self, num_layers: int, logits: bool):
         if self.done != list(range(num_layers)):
@@ -283,36 +270,21 @@ def check_pairs(pairs, n, device) -> torch.Tensor:
     return wide.to(torch.int32).contiguous()
 
 
-class ContactFeatureAccumulator:
-    """What ForwardContext.contacts holds during contact_features: the same `.layer(index, q, k, q_prescaled)` hook as
-    ContactAccumulator; every layer's H features of every pair go into columns index * H .. of the (P, L H) float32 matrix `out`
-    (esme_hip_contact_features).  `pairs`: int32 (P, 3) on the device, already validated.  `keep_qk` (tests): as ContactAccumulator."""
+class ContactFeatureAccumulator(QKObserver):
+    """The observer of contact_features: every layer's H features of every pair go into columns index * H .. of the (P, L H) float32
+    matrix `out` (esme_hip_contact_features).  `pairs`: int32 (P, 3) on the device, already validated."""
 
     def __init__(self, pairs: torch.Tensor, cu_lens: torch.Tensor, max_len: int, num_layers: int, heads: int, head_pad: int, head_dim: int,
                  trim=(1, 1), keep_qk: bool = False):
-        dev = cu_lens.device
-        self.cu_lens, self.max_len, self.heads, self.head_pad = cu_lens, int(max_len), int(heads), int(head_pad)
-        self.scale = float(head_dim) ** -0.5                     # of the LOGICAL head dim
+        super().__init__(cu_lens, max_len, heads, head_pad, head_dim, lambda B, T: _hip_contact_features.workspace_bytes(B, T, heads), keep_qk)
         self.front, self.back = trim
         self.pairs = pairs
-        self.out = torch.empty(pairs.shape[0], int(num_layers) * self.heads, dtype=torch.float32, device=dev)
-        B, T = cu_lens.numel() - 1, int(cu_lens[-1])
-        self.ws = torch.empty(max(_hip_contact_features.workspace_bytes(B, T, heads), 16), dtype=torch.uint8, device=dev)
-        self.done = []
-        self.qk = [] if keep_qk else None
+        self.out = torch.empty(pairs.shape[0], int(num_layers) * self.heads, dtype=torch.float32, device=cu_lens.device)
 
-    def layer(self, index: int, q: torch.Tensor, k: torch.Tensor, q_prescaled: bool) -> None:
-        T = q.shape[0]
-        E = self.heads * self.head_pad
-        q2, k2 = (t.view(T, E) if t.dim() == 3 else t for t in (q, k))
-        if q2.stride(0) != k2.stride(0) or q2.stride(1) != 1 or k2.stride(1) != 1:
-            q2, k2 = q2.contiguous(), k2.contiguous()
-        if self.qk is not None:
-            self.qk.append((index, q2.clone(), k2.clone(), bool(q_prescaled)))
+    def launch(self, index: int, q2: torch.Tensor, k2: torch.Tensor, q_prescaled: bool) -> None:
         if self.out.shape[0]:
             _hip_contact_features.contact_features(q2, k2, self.cu_lens, self.max_len, self.heads, self.head_pad, self.scale, self.pairs, self.out,
                                                    index * self.heads, self.ws, q_prescaled=q_prescaled, trim_front=self.front, trim_back=self.back)
-        self.done.append(index)
 
     def result(self, num_layers: int) -> torch.Tensor:
         if self.done != list(range(num_layers)):

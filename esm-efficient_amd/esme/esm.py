@@ -35,6 +35,7 @@ from esme.attention import FlashTransformerLayer, ForwardContext
 from esme.head import RobertaLMHead
 from esme.embedding import LearnedPositionalEmbedding
 from esme.nn import LayerNorm
+from esme.qk_observer import dense_blocks
 
 model_names = ['esm2_8m', 'esm2_35m', 'esm2_150m', 'esm2_650m', 'esm2_3b', 'esm2_15b',
                'esmc_300m', 'esmc_600m', 'esm1b', 'esm1v']
@@ -321,10 +322,10 @@ class ESM2(nn.Module):
                 x = torch.cat([x[..., i * Ep:i * Ep + E] for i in range(x.shape[-1] // Ep)], dim=-1)
             return x
 
-    def _forward_representation(self, tokens, pad_args, pad_output, pad_indices, layers, want_pair=False, lora_names=None, contacts=None):
+    def _forward_representation(self, tokens, pad_args, pad_output, pad_indices, layers, want_pair=False, lora_names=None, observer=None):
         """forward_representation at the PHYSICAL width (== the logical one unless the layout is padded).  `want_pair`
         (precision 'exact' only): return the (hi, lo) bf16 pair of the final-LayerNorm output, the LM head's operand.
-        `contacts` (predict_contacts, precision 'fast'): called with (cu_lens, max_len), returns the ContactAccumulator that every
+        `observer` (_observe, precision 'fast'): called with (cu_lens, max_len), returns the esme.qk_observer.QKObserver that every
         attention block hands its (q, k) to; the layers then run through the per-layer module loop, as with `layers=[...]`."""
         lora = self._lora_select(lora_names)                   # None without adapters; else the names this call applies
         x = self._embedding_phys(tokens, pad_args)
@@ -343,17 +344,17 @@ class ESM2(nn.Module):
         # its pad_input raises an index error) -- using S keeps the scatter in bounds for fixed-width batches too.
         pad_width = tokens.shape[1] if pad_args is None else max_len
         ctx = self._context(cu_lens, max_len, x.shape[0], x.device)
-        if contacts is not None:
-            ctx.contacts = contacts(cu_lens, max_len)
+        if observer is not None:
+            ctx.observer = observer(cu_lens, max_len)
         # one mode, one method: (final-LayerNorm output, raw outputs of the layers in `layers`).  'high' without layers is the fast path.
         mode = self.precision if self.precision in ('half', 'exact') or (self.precision == 'high' and len(self.layers)) else 'fast'
         x, taps = getattr(self, '_run_' + mode)(x, (tokens, pad_args, pad_indices), cu_lens, max_len, ctx, layers, want_pair, lora)
         return self._finish_representation(x, taps, pad_output, pad_args, pad_indices, cu_lens, pad_width)
 
     def _one_call(self, ctx, layers, mode) -> bool:
-        """May this forward take the one-call C entry of `mode` (esme.cforward)?  Not with `layers=[...]` taps, a contact accumulator or an
+        """May this forward take the one-call C entry of `mode` (esme.cforward)?  Not with `layers=[...]` taps, a (q, k) observer or an
         active launch trace: those need the per-layer module loop."""
-        return bool(self.c_forward and not layers and ctx.contacts is None and _hip.TRACE is None and self._c_forward_ok(mode))
+        return bool(self.c_forward and not layers and ctx.observer is None and _hip.TRACE is None and self._c_forward_ok(mode))
 
     def _final_pair(self, T, device, pair=None):
         """'exact' / 'half': the final LayerNorm's (hi, lo) bf16 pair (or the one given) and its fp32 output."""
@@ -505,30 +506,33 @@ class ESM2(nn.Module):
         'fast' with one extra kernel call per layer (esme_hip_contact_layer); no attention map is stored."""
         if self.contact_head is None:
             raise RuntimeError('predict_contacts: the model has no contact head (model.set_contact_head(head or path); ESM-C ships none)')
-        if self.precision != 'fast':
-            raise NotImplementedError(f"predict_contacts runs in precision 'fast' only; precision {self.precision!r} is not implemented "
-                                      "(set_precision('fast'))")
         from esme.contacts import ContactAccumulator
-        head, box = self.contact_head, []
+        head = self.contact_head
+        acc = self._observe('predict_contacts', tokens, pad_args, lora_names, _keep_qk,
+                            lambda cu_lens, max_len, *hd: ContactAccumulator(head, cu_lens, max_len, *hd, keep_qk=_keep_qk))
+        maps = acc.result(len(self.layers), logits)
+        if not (pad_output or pad_args is None):
+            return maps
+        width = (tokens.shape[1] if pad_args is None else acc.max_len) - sum(head.trim)
+        return dense_blocks(maps, (), width, torch.float32, acc.out.device)
 
-        def make(cu_lens, max_len):
-            box.append(ContactAccumulator(head, cu_lens, max_len, self.attention_heads, self.head_pad,
-                                          self.embed_dim // self.attention_heads, keep_qk=_keep_qk))
+    def _observe(self, what, tokens, pad_args, lora_names, keep_qk, make):
+        """The packed forward of `what` (predict_contacts / contact_features / attention_maps) with a (q, k) observer installed:
+        `make(cu_lens, max_len, heads, head_pad, head_dim)` builds it once the batch's geometry is known, every attention block hands
+        it its final (q, k), and it is returned.  `keep_qk` (tests): its `.qk` is left in `self._contact_qk`."""
+        if self.precision != 'fast':
+            raise NotImplementedError(f"{what} runs in precision 'fast' only; precision {self.precision!r} is not implemented "
+                                      "(set_precision('fast'))")
+        box = []
+
+        def observer(cu_lens, max_len):
+            box.append(make(cu_lens, max_len, self.attention_heads, self.head_pad, self.embed_dim // self.attention_heads))
             return box[0]
         with _hip.stream_scope(self.embed_tokens.weight.device):
-            self._forward_representation(tokens, pad_args, False, None, [], lora_names=lora_names, contacts=make)
-            acc = box[0]
-            maps = acc.result(len(self.layers), logits)
-            if _keep_qk:
-                self._contact_qk = acc.qk
-            if not (pad_output or pad_args is None):
-                return maps
-            f, e = head.trim
-            width = (tokens.shape[1] if pad_args is None else acc.max_len) - f - e
-            out = torch.zeros(len(maps), max(width, 0), max(width, 0), dtype=torch.float32, device=acc.out.device)
-            for i, m in enumerate(maps):
-                out[i, :m.shape[0], :m.shape[1]] = m
-            return out
+            self._forward_representation(tokens, pad_args, False, None, [], lora_names=lora_names, observer=observer)
+        if keep_qk:
+            self._contact_qk = box[0].qk
+        return box[0]
 
     def contact_features(self, tokens, pad_args=None, pairs=None, min_sep=0, lora_names=None, _keep_qk=False):
         """The contact regression's features at residue pairs: (X, pairs), X float32 (P, num_layers * attention_heads) on the device with
@@ -538,24 +542,14 @@ class ESM2(nn.Module):
         tensor of (i, j) rows per sequence -- ValueError on a row out of range.  Needs no contact head: this is what
         ContactHead.fit is trained on.  Runs the forward in precision 'fast' with one extra kernel call per layer
         (esme_hip_contact_features); no attention map is stored."""
-        if self.precision != 'fast':
-            raise NotImplementedError(f"contact_features runs in precision 'fast' only; precision {self.precision!r} is not implemented "
-                                      "(set_precision('fast'))")
         from esme.contacts import ContactFeatureAccumulator, all_pairs, check_pairs
-        box = []
 
-        def make(cu_lens, max_len):
+        def make(cu_lens, max_len, *hd):
             n = (cu_lens[1:] - cu_lens[:-1] - 2).clamp(min=0).tolist()          # the alphabets put one bos and one eos around every protein
             rows = all_pairs(n, min_sep, cu_lens.device) if pairs is None else check_pairs(pairs, n, cu_lens.device)
-            box.append(ContactFeatureAccumulator(rows, cu_lens, max_len, len(self.layers), self.attention_heads, self.head_pad,
-                                                 self.embed_dim // self.attention_heads, trim=(1, 1), keep_qk=_keep_qk))
-            return box[0]
-        with _hip.stream_scope(self.embed_tokens.weight.device):
-            self._forward_representation(tokens, pad_args, False, None, [], lora_names=lora_names, contacts=make)
-            acc = box[0]
-            if _keep_qk:
-                self._contact_qk = acc.qk
-            return acc.result(len(self.layers)), acc.pairs
+            return ContactFeatureAccumulator(rows, cu_lens, max_len, len(self.layers), *hd, trim=(1, 1), keep_qk=_keep_qk)
+        acc = self._observe('contact_features', tokens, pad_args, lora_names, _keep_qk, make)
+        return acc.result(len(self.layers)), acc.pairs
 
     # -- attention maps (esme/attention_maps.py) -----------------------------------------
     def attention_maps(self, tokens, pad_args=None, pad_output=False, layers=None, heads=None, head_weights=None,
@@ -570,9 +564,6 @@ class ESM2(nn.Module):
         L_sel * n_out * sum_b S_b^2 * itemsize bytes (n_out = H_sel, or 1 with head_weights): ValueError before the forward runs when
         that exceeds `max_bytes`.  Runs the forward in precision 'fast' with one extra kernel call per SELECTED layer
         (esme_hip_attn_maps)."""
-        if self.precision != 'fast':
-            raise NotImplementedError(f"attention_maps runs in precision 'fast' only; precision {self.precision!r} is not implemented "
-                                      "(set_precision('fast'))")
         from esme import attention_maps as AM
         if dtype not in AM.DTYPES:
             raise ValueError(f'attention_maps: dtype must be torch.float32 or torch.bfloat16, got {dtype}')
@@ -590,26 +581,13 @@ class ESM2(nn.Module):
                              f'{sum(s * s for s in lengths)} * {2 if dtype == torch.bfloat16 else 4}), more than '
                              f'max_bytes = {max_bytes}: select fewer layers= or heads=, pass head_weights= (one map per layer), use '
                              'dtype=torch.bfloat16, send fewer or shorter proteins per call, or raise max_bytes=')
-        box = []
-
-        def make(cu_lens, max_len):
-            box.append(AM.AttentionMapAccumulator(lsel, hsel, weights, dtype, cu_lens, max_len, self.attention_heads, self.head_pad,
-                                                  self.embed_dim // self.attention_heads, keep_qk=_keep_qk))
-            return box[0]
-        with _hip.stream_scope(self.embed_tokens.weight.device):
-            self._forward_representation(tokens, pad_args, False, None, [], lora_names=lora_names, contacts=make)
-            acc = box[0]
-            maps = acc.result()
-            if _keep_qk:
-                self._contact_qk = acc.qk
-            if not (pad_output or pad_args is None):
-                return maps
-            width = tokens.shape[1] if pad_args is None else acc.max_len
-            lead = (len(lsel),) if weights is not None else (len(lsel), n_out)
-            out = torch.zeros(len(maps), *lead, width, width, dtype=dtype, device=acc.out.device)
-            for i, m in enumerate(maps):
-                out[i, ..., :m.shape[-2], :m.shape[-1]] = m
-            return out
+        acc = self._observe('attention_maps', tokens, pad_args, lora_names, _keep_qk,
+                            lambda *geometry: AM.AttentionMapAccumulator(lsel, hsel, weights, dtype, *geometry, keep_qk=_keep_qk))
+        maps = acc.result()
+        if not (pad_output or pad_args is None):
+            return maps
+        lead = (len(lsel),) if weights is not None else (len(lsel), n_out)
+        return dense_blocks(maps, lead, tokens.shape[1] if pad_args is None else acc.max_len, dtype, acc.out.device)
 
     def graphed(self, tokens, pad_args, what: str = 'forward', clone: bool = True):
         """`getattr(self, what)(tokens, pad_args)` replayed from a hipGraph captured on first use of this

@@ -228,3 +228,13 @@ def test_refusals_by_name_need_no_device():
     tokens, pad = torch.zeros(12, dtype=torch.long), (torch.tensor([0, 5, 12], dtype=torch.int32), 7)
     with pytest.raises(NotImplementedError, match='attention_maps'):
         model.graphed(tokens, pad, what='attention_maps')
+
+
+def test_the_three_accumulators_share_one_layer_hook():
+    from esme.attention_maps import AttentionMapAccumulator
+    from esme.contacts import ContactAccumulator, ContactFeatureAccumulator
+    from esme.qk_observer import QKObserver
+    for cls in (ContactAccumulator, ContactFeatureAccumulator, AttentionMapAccumulator):
+        assert issubclass(cls, QKObserver) and cls is not QKObserver
+        assert 'layer' not in vars(cls) and cls.layer is QKObserver.layer
+        assert 'launch' in vars(cls) and 'result' in vars(cls)

@@ -399,3 +399,30 @@ def test_default_forward_launches_nothing_new(monkeypatch):
     model.attention_maps(tokens, (cu, ml), layers=[0, 2], heads=[0])
     monkeypatch.undo()
     assert called.count('esme_hip_attn_maps') == 2 and called.count('esme_hip_attn_maps_workspace_bytes') == 1
+
+
+def test_statistics_are_the_contact_kernels_bit_for_bit():
+    """attn_map_stats_kernel and contact_stats_kernel are one pass (softmax_row_stats of csrc/score_tiles.h): on the same (q, k, cu_lens)
+    the row maxima m and row sums l that esme_hip_attn_maps leaves in its workspace (ws, ws + n_heads * T) for the head list [0, 1] have
+    the bits of those esme_hip_contact_layer leaves (ws, ws + H * T) without a trim."""
+    from esme import _hip, _hip_attn_maps as HM, _hip_contacts as HC
+    d, heads, lengths = 32, 2, (2, 3, 65)
+    layers, cu, scale = MB.make_operands(lengths, heads, d, seed=23, device=DEV)
+    q, k, qp = layers[0]
+    B, T = len(lengths), int(cu[-1])
+    ws_m = torch.full((HM.workspace_bytes(B, T, heads),), 0xFF, dtype=torch.uint8, device=DEV)
+    ws_c = torch.full((HC.workspace_bytes(B, T, heads),), 0xFF, dtype=torch.uint8, device=DEV)
+    _, off_m, total_m = HM.map_offsets(cu, heads)
+    _, off_c, total_c = HC.map_offsets(cu, 0, 0)
+    out_m = torch.empty(total_m, dtype=F32, device=DEV)
+    out_c = torch.empty(total_c, dtype=F32, device=DEV)
+    with _hip.stream_scope(DEV):
+        HM.attn_maps(q, k, cu, max(lengths), heads, d, scale, torch.tensor([0, 1], dtype=torch.int32, device=DEV), out_m, off_m, 0, ws_m,
+                     q_prescaled=qp)
+        HC.contact_layer(q, k, cu, max(lengths), heads, d, scale, torch.ones(heads, dtype=F32, device=DEV), 0.0, True, out_c, off_c, ws_c,
+                         q_prescaled=qp, trim_front=0, trim_back=0)
+    torch.cuda.synchronize()
+    stats_m = ws_m.view(F32)[:2 * heads * T].view(2, heads, T)
+    stats_c = ws_c.view(F32)[:2 * heads * T].view(2, heads, T)
+    assert bool(torch.isfinite(stats_m).all()) and bool((stats_m[1] >= 1.0).all())     # every row written; l holds the maximum's exp2(0)
+    assert torch.equal(stats_m.view(torch.int32), stats_c.view(torch.int32))
