@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from esme import _hip
-from esme.nn import GELU, Derived, LayerNorm, Linear, weights_epoch
+from esme.nn import GELU, Derived, LayerNorm, Linear, pad_last, pad_rows, version_key
 from esme.rotary import RotaryEmbedding
 
 # head dim 64 / 32 with fused rotary: softmax_scale * log2(e) folded into q by the QKV epilogue, attention without a reference maximum
@@ -124,29 +124,6 @@ def head_slots(heads: int, d: int, dp: int, device=None) -> torch.Tensor:
     c = torch.arange(d, device=device)
     within = torch.where(c < d // 2, c, dp // 2 + c - d // 2)
     return (torch.arange(heads, device=device).unsqueeze(1) * dp + within.unsqueeze(0)).reshape(-1)
-
-
-def _pad_last(t: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
-    """Zero-pad the last dim of a weight / vector to n."""
-    if t is None or t.shape[-1] == n:
-        return t
-    out = torch.zeros(*t.shape[:-1], n, dtype=t.dtype, device=t.device)
-    out[..., :t.shape[-1]] = t
-    return out
-
-
-def _pad_rows(t: torch.Tensor, n: int) -> torch.Tensor:
-    if t.shape[0] == n:
-        return t
-    out = torch.zeros(n, *t.shape[1:], dtype=t.dtype, device=t.device)
-    out[:t.shape[0]] = t
-    return out
-
-
-def _version_key(*params):
-    """Cache key of a copy derived from `params`: their addresses and version counters, and the weight-edit epoch (esme.nn.weights_epoch: moved
-    by ESM2.invalidate_graphs after in-place writes that bump no version counter)."""
-    return (weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in params if p is not None)
 
 
 def _check_fp16_range(w16: torch.Tensor) -> None:
@@ -369,7 +346,7 @@ class FlashMultiheadAttention(nn.Module):
 
     # -- weight layout ------------------------------------------------------
     def _pack_key(self):
-        return _version_key(self.q.weight, self.k.weight, self.v.weight, self.q.bias, self.k.bias, self.v.bias,
+        return version_key(self.q.weight, self.k.weight, self.v.weight, self.q.bias, self.k.bias, self.v.bias,
                             *((self.out.weight, self.out.bias) if self.padded else ()))
 
     def _pack(self):
@@ -402,18 +379,18 @@ class FlashMultiheadAttention(nn.Module):
                 b[i * Ea + slots] = lin.bias.data
         ow = torch.zeros(Ep, Ea, dtype=w.dtype, device=w.device)
         ow[:E, slots] = self.out.weight.data
-        return w, b, ow, _pad_last(self.out.bias.data, Ep) if self.out.bias is not None else None
+        return w, b, ow, pad_last(self.out.bias.data, Ep) if self.out.bias is not None else None
 
     def _fold_operands(self):
         w, b, _, _ = self._pack()
-        return (w, b, _pad_last(self.norm.weight.data, self.phys_dim),
-                _pad_last(self.norm.bias.data, self.phys_dim) if self.norm.bias is not None else None)
+        return (w, b, pad_last(self.norm.weight.data, self.phys_dim),
+                pad_last(self.norm.bias.data, self.phys_dim) if self.norm.bias is not None else None)
 
     def _pack_fold(self, f16: bool = False):
         """LN-folded copy of the fused QKV weight (self.norm folded in): (W', c1, c2); `f16`: ((W', c1, c2), (rho, 1 / rho)) with W' in
         float16 (precision 'half')."""
         self._pack()
-        return self._derived.get('fold16' if f16 else 'fold', (self._derived.key('pack'), _version_key(self.norm.weight, self.norm.bias)),
+        return self._derived.get('fold16' if f16 else 'fold', (self._derived.key('pack'), version_key(self.norm.weight, self.norm.bias)),
                                  _build_fold, f16, self._fold_operands)
 
     def stream_scale(self):
@@ -450,7 +427,7 @@ class FlashMultiheadAttention(nn.Module):
             if self._q4_out is not None:
                 raise NotImplementedError("precision='half' needs unquantised weights")
             w, b = self._weights_out()
-            return self._derived.get('out16', _version_key(w), _to_f16, w), b
+            return self._derived.get('out16', version_key(w), _to_f16, w), b
         if self._q4_out is not None:
             return self._q4_out.plain()
         if self.padded:
@@ -631,12 +608,12 @@ class FlashMultiheadAttention(nn.Module):
         if quantised:
             # the key of the unquantised form minus the base weight; the folded A' carries the LayerNorm, so its version stays
             key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), 'quantised base',
-                   _version_key(*params, *((self.norm.weight, self.norm.bias) if fold else ())))
+                   version_key(*params, *((self.norm.weight, self.norm.bias) if fold else ())))
             base = None
         else:
             base = (self._pack_fold() if fold else self._pack())[0]
             key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), self._derived.key('fold' if fold else 'pack'),
-                   _version_key(self.out.weight, *params))
+                   version_key(self.out.weight, *params))
 
         def extended(w, rows, X):
             """(the weight form, its extension columns as a view): (rows, E + X) zeros with the base `w` in the first E columns; on a
@@ -755,7 +732,7 @@ class SwiGLU(nn.Module):
         self._derived = Derived()   # 'pack': the interleaved weight
 
     def _pack(self):
-        return self._derived.get('pack', _version_key(self.activation.weight, self.fc.weight), self._build_pack)
+        return self._derived.get('pack', version_key(self.activation.weight, self.fc.weight), self._build_pack)
 
     def _build_pack(self):
         F, E = self.activation.weight.shape
@@ -806,7 +783,7 @@ class FlashTransformerLayer(nn.Module):
         beta = ln.bias.data if ln.bias is not None else None
         if self.final_activation == 'gelu':
             up, Ep = self.final[1], self.phys_dim
-            return _pad_last(up.weight.data, Ep), up.bias.data if up.bias is not None else None, _pad_last(ln.weight.data, Ep), _pad_last(beta, Ep)
+            return pad_last(up.weight.data, Ep), up.bias.data if up.bias is not None else None, pad_last(ln.weight.data, Ep), pad_last(beta, Ep)
         return self.final[1]._pack(), None, ln.weight.data, beta
 
     def _pack_fold(self, f16: bool = False):
@@ -815,11 +792,11 @@ class FlashTransformerLayer(nn.Module):
         ln = self.final[0]
         if self.final_activation == 'gelu':
             up = self.final[1]
-            key = _version_key(up.weight, up.bias, ln.weight, ln.bias)
+            key = version_key(up.weight, up.bias, ln.weight, ln.bias)
         else:
             sw = self.final[1]
             sw._pack()
-            key = (sw._derived.key('pack'), _version_key(ln.weight, ln.bias))
+            key = (sw._derived.key('pack'), version_key(ln.weight, ln.bias))
         return self._derived.get('fold16' if f16 else 'fold', key, _build_fold, f16, self._fold_operands)
 
     def stream_scale(self):
@@ -849,7 +826,7 @@ class FlashTransformerLayer(nn.Module):
             if self.final_activation != 'gelu':
                 raise NotImplementedError('padded layouts are implemented for the ESM-2 block')
             up = self.final[1]
-            return self._derived.get('up_pad', _version_key(up.weight), lambda: _pad_last(up.weight.data, self.phys_dim)), up.bias, None, None
+            return self._derived.get('up_pad', version_key(up.weight), lambda: pad_last(up.weight.data, self.phys_dim)), up.bias, None, None
         if self.final_activation == 'gelu':
             return self.final[1].weight, self.final[1].bias, None, None
         return self.final[1]._pack(), None, None, None
@@ -859,13 +836,13 @@ class FlashTransformerLayer(nn.Module):
             if self._q4_down is not None:
                 raise NotImplementedError("precision='half' needs unquantised weights")
             w, b = self._weights_down()
-            return self._derived.get('down16', _version_key(w), _to_f16, w), b
+            return self._derived.get('down16', version_key(w), _to_f16, w), b
         if self._q4_down is not None:
             return self._q4_down.plain()
         down = self.final[3] if self.final_activation == 'gelu' else self.final[2]
         if self.padded:                                     # zero rows / bias entries for the pad columns of the stream
-            return self._derived.get('down_pad', _version_key(down.weight, down.bias), lambda: (
-                _pad_rows(down.weight.data, self.phys_dim), _pad_last(down.bias.data, self.phys_dim) if down.bias is not None else None))
+            return self._derived.get('down_pad', version_key(down.weight, down.bias), lambda: (
+                pad_rows(down.weight.data, self.phys_dim), pad_last(down.bias.data, self.phys_dim) if down.bias is not None else None))
         return down.weight, down.bias
 
     def _ffn(self, x, alpha, stream, x_stats=None, stats_out=None, ovf=None):

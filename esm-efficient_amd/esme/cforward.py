@@ -13,7 +13,7 @@ import operator
 
 import torch
 
-from esme import _hip
+from esme import _hip, attention
 from esme._hip import LayerWeights, ModelDesc
 
 
@@ -62,8 +62,7 @@ class ModelDescriptor:
         ln = model.emb_layer_norm_after
         d.final_ln_w, d.final_ln_b = _ptr(ln.weight), _ptr(ln.bias)
         if not exact:
-            from esme.attention import _ATTN_QP
-            d.attn_q_prescale = int(bool(plan is not None and plan.qp)) if f16 else int(_ATTN_QP)      # ONE flag drives both paths (esme.attention reads it the same way; 'half': the plan's)
+            d.attn_q_prescale = int(bool(plan is not None and plan.qp)) if f16 else int(attention._ATTN_QP)      # ONE flag drives both paths (esme.attention reads it the same way; 'half': the plan's)
         if plan is not None:
             if plan.ext_sel is not None:
                 d.half_ext_n, d.half_ext_sel = int(plan.ext_sel.numel()), _ptr(plan.ext_sel)

@@ -31,10 +31,10 @@ from torch import nn
 
 from esme import _hip, halfmode
 from esme.alphabet import Alphabet, Alphabet3
-from esme.attention import FlashTransformerLayer, ForwardContext
+from esme.attention import FlashTransformerLayer, ForwardContext, padded_head_dim
 from esme.head import RobertaLMHead
 from esme.embedding import LearnedPositionalEmbedding
-from esme.nn import LayerNorm
+from esme.nn import Derived, LayerNorm, bump_epoch, bump_weights_epoch, pad_last, version_key
 from esme.qk_observer import dense_blocks
 
 model_names = ['esm2_8m', 'esm2_35m', 'esm2_150m', 'esm2_650m', 'esm2_3b', 'esm2_15b',
@@ -99,12 +99,10 @@ class ESM2(nn.Module):
         # Physical layout: the GEMM walks K in tiles of 64 and the attention kernels know head dims
         # 16/32/64/128, so a model like ESM2-35M (E = 480, d = 24) runs with a 512-wide residual stream
         # (zero pad columns) and 32-wide heads.  The padding lives in derived weight copies only.
-        from esme.attention import padded_head_dim
         self.phys_dim = (embed_dim + 63) // 64 * 64
         self.head_pad = padded_head_dim(embed_dim // attention_heads)
         self.padded = self.phys_dim != embed_dim or self.head_pad != embed_dim // attention_heads
-        self._embed_pad = None
-        self._embed_pad_key = None
+        self._derived = Derived()                  # the embedding table at the physical width
         self.checkpointing = False
         self.embed_scale = 1
         self.half_mode = halfmode.HalfState()      # precision 'half': plan, guard, range flag (esme.halfmode)
@@ -142,14 +140,7 @@ class ESM2(nn.Module):
         w = self.embed_tokens.weight
         if not self.padded:
             return w
-        from esme.attention import _version_key
-        key = _version_key(w)
-        if key != self._embed_pad_key:
-            from esme.attention import _pad_last
-            with torch.no_grad():
-                self._embed_pad = _pad_last(w.data, self.phys_dim)
-            self._embed_pad_key = key
-        return self._embed_pad
+        return self._derived.get('embed', version_key(w), pad_last, w.data, self.phys_dim)
 
     # ESME_CHECK_TOKENS=1 (or model.debug_checks = True): every forward validates its token ids on the device first -- one synchronisation per call.
     # The reference's nn.Embedding raises on an id outside the table (esme/esm.py:176-199); esme_hip_embed writes a zero row instead (no trap on the hot
@@ -615,9 +606,8 @@ class ESM2(nn.Module):
         weights in place, in particular through `p.data`, which bumps no version counter: the next 'half' forward recalibrates on the
         edited weights (a plan decided on the old ones would keep their massive channels and score bounds), and every derived weight copy
         (LN-folded, fp16, extension-tile, packed, padded) is rebuilt from them on next use."""
-        from esme.nn import bump_weights_epoch
         self.half_mode.plan = None
-        bump_weights_epoch()                  # every derived weight copy is rebuilt on next use (its key holds the epoch: esme.attention._version_key)
+        bump_weights_epoch()                  # every derived weight copy is rebuilt on next use (its key holds the epoch: esme.nn.version_key)
         self._drop_derived()
 
     def _drop_derived(self):
@@ -629,7 +619,6 @@ class ESM2(nn.Module):
         self.__dict__.pop('_cdesc_exact', None)
         self.__dict__.pop('_cparams', None)
         self.__dict__.pop('_cws', None)
-        from esme.nn import bump_epoch
         bump_epoch()
 
     # -- LoRA adapters (inference; esme/lora.py) ---------------------------------------------------------------------

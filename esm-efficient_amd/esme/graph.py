@@ -18,28 +18,24 @@ from collections import OrderedDict
 
 import torch
 
-from esme.nn import Derived, flatten_tensors
-
-# DERIVED device tensors (packed / LayerNorm-folded / padded weight copies, rotary tables) are allocated outside a graph's private pool and
-# read by the captured kernels through raw pointers.  The transformer block keeps its own in an esme.nn.Derived per module (found by type,
-# whatever it holds); these are the attributes under which the other modules cache theirs
-_DERIVED_ATTRS = ('_pad', '_embed_pad', '_cos_cached', '_sin_cached', '_table_cache')
+# Device tensors a kernel reads that are not its inputs (packed / LayerNorm-folded / padded weight copies, rotary tables, quantised codes
+# and their expansion scratch, the state of precision 'half') are allocated outside a graph's private pool and read by the captured kernels
+# through raw pointers.  One rule finds them: besides parameters and buffers, each lives in an object that is an attribute of some module
+# and enumerates its tensors with `tensors()` (esme.nn.Derived and the plain state objects alike); no name is listed here.
 
 
 def external_tensors(model):
-    """Every derived tensor a forward of `model` reads that lives outside the capture pool.  A captured graph
-    keeps strong references to them: modules REPLACE such tensors (the rotary cache regrows when a longer
-    batch arrives; weight copies are rebuilt after a parameter update) and the replaced ones would otherwise
-    be freed while an older graph still holds their addresses."""
-    keep = []
+    """Every tensor a forward of `model` reads that lives outside the capture pool: the parameters and buffers, and the tensors of
+    every attribute of every module that offers `tensors()`.  A captured graph keeps strong references to them: their owners REPLACE
+    such tensors (the rotary tables and the quantised layers' scratch regrow when a longer batch or a larger matrix arrives; weight
+    copies are rebuilt after a parameter update) and the replaced ones would otherwise be freed while an older graph still holds
+    their addresses."""
+    keep = [p.data for p in model.parameters()]
+    keep.extend(model.buffers())
     for m in model.modules():
         for v in vars(m).values():
-            if isinstance(v, Derived):
+            if callable(getattr(v, 'tensors', None)):
                 keep.extend(v.tensors())
-        for a in _DERIVED_ATTRS:
-            keep.extend(flatten_tensors(getattr(m, a, None)))
-    keep.extend(p.data for p in model.parameters())
-    keep.extend(model.half_mode.tensors())                # precision 'half': the plan's channel list, the guard's maxima and the range flag the captured kernels read / write
     return keep
 
 

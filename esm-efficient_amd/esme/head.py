@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from esme import _hip
-from esme.nn import LayerNorm, Linear
+from esme.nn import Derived, LayerNorm, Linear, pad_last, pad_rows, version_key
 from esme.pooling import PartitionMeanPool, _ReluMLP
 
 
@@ -23,19 +23,14 @@ class RobertaLMHead(nn.Module):
         self.dense = Linear(embed_dim, embed_dim, dtype=dtype)
         self.layer_norm = LayerNorm(embed_dim, dtype=dtype)
         self.final = Linear(embed_dim, vocab_size, dtype=dtype)
-        self._pad = None
-        self._pad_key = None
+        self._derived = Derived()
 
     def _padded_weights(self):
-        from esme.attention import _pad_last, _pad_rows, _version_key
-        key = _version_key(self.dense.weight, self.dense.bias, self.final.weight)
-        if key != self._pad_key:
-            Ep = self.phys_dim
-            with torch.no_grad():
-                self._pad = (_pad_rows(_pad_last(self.dense.weight.data, Ep), Ep), _pad_last(self.dense.bias.data, Ep),
-                             _pad_last(self.final.weight.data, Ep))
-            self._pad_key = key
-        return self._pad
+        return self._derived.get('pad', version_key(self.dense.weight, self.dense.bias, self.final.weight), self._build_padded)
+
+    def _build_padded(self):
+        Ep = self.phys_dim
+        return (pad_rows(pad_last(self.dense.weight.data, Ep), Ep), pad_last(self.dense.bias.data, Ep), pad_last(self.final.weight.data, Ep))
 
     def forward_exact(self, pair):
         """Split-operand ('exact' / 'half') modes: `pair` (T, 2 E_phys) = [hi | lo] of the final-LayerNorm output -> fp32 logits (T, V)."""

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from esme import _hip
+from esme.nn import Derived, version_key
 
 EXT_TILE = 64            # the GEMM's K tile: extension widths are multiples of it
 MAX_EXT = 256            # widest extension esme_hip_lora_down is built for
@@ -59,7 +60,7 @@ class LoRA(nn.Module):
         self.lora_A = nn.ParameterDict({n: nn.Parameter(torch.zeros(rank, self.in_features, device=ref.device, dtype=dtype)) for n in names})
         self.lora_B = nn.ParameterDict({n: nn.Parameter(torch.zeros(self.out_features, rank, device=ref.device, dtype=dtype)) for n in names})
         self.reset_parameters()
-        self._ext = None         # (key, [W | s B | 0], stacked A): the standalone forward's derived weights
+        self._derived = Derived()         # 'ext': ([W | s B | 0], stacked A), the standalone forward's weights
 
     def reset_parameters(self):
         for n in self.lora_A:
@@ -97,26 +98,29 @@ class LoRA(nn.Module):
     def params(self, names: tuple):
         return [p for n in names for p in (self.lora_A[n], self.lora_B[n])]
 
+    def stage_form(self, names=None):
+        """([W | s B | 0] (out, in + X) bf16, stacked A) of the adapters `names` (select()): the operands of the standalone forward."""
+        names = self.select(names)
+        w = self.layer.weight
+        if w.dtype != torch.bfloat16:
+            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters)')
+        return self._derived.get('ext', (names, float(self.scaling), version_key(w, *self.params(names))), self._build_stage_form, names)
+
+    def _build_stage_form(self, names: tuple):
+        w = self.layer.weight
+        A, B = self.stacked(names)
+        K, X = w.shape[1], ext_width(A.shape[0])
+        we = torch.zeros(w.shape[0], K + X, dtype=torch.bfloat16, device=w.device)
+        we[:, :K] = w.data
+        we[:, K:K + B.shape[1]] = B.to(torch.bfloat16)
+        return we, A.contiguous()
+
     def forward(self, x: torch.Tensor, names=None):
         """layer(x) + sum_n scaling * B_n A_n x as ONE GEMM over [x | x A^T] (the stage form; the model's hot path fuses the
         adapters of q, k and v into its packed QKV GEMM: esme.attention.FlashMultiheadAttention)."""
         if self.training:
             raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
-        from esme.attention import _version_key
-        names = self.select(names)
-        w, b = self.layer.weight, self.layer.bias
-        if w.dtype != torch.bfloat16:
-            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters)')
-        key = (names, float(self.scaling), _version_key(w, *self.params(names)))
-        if self._ext is None or self._ext[0] != key:
-            with torch.no_grad():
-                A, B = self.stacked(names)
-                K, X = w.shape[1], ext_width(A.shape[0])
-                we = torch.zeros(w.shape[0], K + X, dtype=torch.bfloat16, device=w.device)
-                we[:, :K] = w.data
-                we[:, K:K + B.shape[1]] = B.to(torch.bfloat16)
-            self._ext = (key, we, A.contiguous())
-        _, we, A = self._ext
+        (we, A), b = self.stage_form(names), self.layer.bias
         shape = x.shape
         x2 = x.reshape(-1, shape[-1])
         K, X = x2.shape[1], we.shape[1] - x2.shape[1]

@@ -7,6 +7,7 @@ the C ABI (`esme._hip`).
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 from torch import nn
@@ -29,7 +30,7 @@ def param_epoch() -> int:
 
 
 # Weight-edit epoch: bumped by ESM2.invalidate_graphs() (and so by load_state_dict / `.to()`), the documented step after writing weights in place --
-# through `p.data` in particular, which moves no version counter.  esme.attention._version_key mixes it into EVERY derived-weight cache key (LN-folded,
+# through `p.data` in particular, which moves no version counter.  version_key mixes it into EVERY derived-weight cache key (LN-folded,
 # fp16, extension-tile, packed, padded copies), so that no cache can be left out of an invalidation.  Global: another model's caches rebuild once too.
 _WEIGHTS_EPOCH = [0]
 
@@ -40,6 +41,29 @@ def bump_weights_epoch() -> None:
 
 def weights_epoch() -> int:
     return _WEIGHTS_EPOCH[0]
+
+
+def version_key(*params):
+    """Cache key of a copy derived from `params`: their addresses and version counters, and the weight-edit epoch (weights_epoch: moved
+    by ESM2.invalidate_graphs after in-place writes that bump no version counter)."""
+    return (weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in params if p is not None)
+
+
+def pad_last(t: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
+    """Zero-pad the last dim of a weight / vector to n."""
+    if t is None or t.shape[-1] == n:
+        return t
+    out = torch.zeros(*t.shape[:-1], n, dtype=t.dtype, device=t.device)
+    out[..., :t.shape[-1]] = t
+    return out
+
+
+def pad_rows(t: torch.Tensor, n: int) -> torch.Tensor:
+    if t.shape[0] == n:
+        return t
+    out = torch.zeros(n, *t.shape[1:], dtype=t.dtype, device=t.device)
+    out[:t.shape[0]] = t
+    return out
 
 
 def flatten_tensors(x):
@@ -55,8 +79,9 @@ def flatten_tensors(x):
 
 
 class Derived:
-    """The derived weight copies of ONE module (packed, LayerNorm-folded, fp16, extension-tile, padded, adapter forms): name -> (key, value).
-    Everything a module's kernels read that is not a parameter lives here, so esme.graph.external_tensors finds it without knowing names."""
+    """The derived tensors of ONE owner (packed, LayerNorm-folded, fp16, extension-tile, padded, adapter forms of its weights; rotary tables):
+    name -> (key, value).  Everything its kernels read that is neither an input nor a parameter lives here or in another object with
+    `tensors()`, so esme.graph.external_tensors finds it without knowing names."""
     __slots__ = ('_entries',)
 
     def __init__(self):
@@ -96,7 +121,7 @@ def weight_t(lin) -> torch.Tensor:
     if d is None:
         d = lin.__dict__['_derived'] = Derived()
     w = lin.weight
-    return d.get('wt', (weights_epoch(), w.data_ptr(), w._version), _transposed, w)
+    return d.get('wt', version_key(w), _transposed, w)
 
 
 def _transposed(w):

@@ -28,7 +28,7 @@ import torch
 from torch import nn
 
 from esme import _hip
-from esme.nn import Linear
+from esme.nn import Derived, Linear, pad_last, version_key
 
 
 def partition_mean_pool(embed: torch.Tensor, cu_lens: torch.Tensor) -> torch.Tensor:
@@ -63,24 +63,25 @@ def _check_embed(embed: torch.Tensor, embed_dim: int) -> None:
         raise ValueError(f'attention pooling: embed must be (T, {embed_dim}), got {tuple(embed.shape)}')
 
 
+def _padded_weight(w, kp):
+    return pad_last(w.data, kp).contiguous()
+
+
 class _ReluMLP:
     """y = final(relu(linear(x))) for the heads: `linear` on the MFMA GEMM (bf16 x: esme_hip_gemm_bf16; fp32 x: the split-operand GEMM
     on the (hi, lo) pair of x with an fp32 result, as RobertaLMHead.forward_exact), then esme_hip_relu_linear.  When the input width is
-    not a multiple of 64 (E = 480), x and the weight are zero-padded to the next multiple (the padded weight is cached by _version_key)."""
+    not a multiple of 64 (E = 480), x and the weight are zero-padded to the next multiple (the padded weight is cached by version_key)."""
 
     def __init__(self):
-        self._pad, self._pad_key = None, None
+        self._derived = Derived()
+
+    def tensors(self):
+        return self._derived.tensors()
 
     def _weight(self, lin: Linear, kp: int) -> torch.Tensor:
         if kp == lin.in_features:
             return lin.weight
-        from esme.attention import _pad_last, _version_key
-        key = (kp, _version_key(lin.weight))
-        if key != self._pad_key:
-            with torch.no_grad():
-                self._pad = _pad_last(lin.weight.data, kp).contiguous()
-            self._pad_key = key
-        return self._pad
+        return self._derived.get('pad', (kp, version_key(lin.weight)), _padded_weight, lin.weight, kp)
 
     def __call__(self, x: torch.Tensor, lin: Linear, final: Linear) -> torch.Tensor:
         M, K = x.shape

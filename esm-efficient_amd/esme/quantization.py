@@ -67,6 +67,9 @@ class WeightScratch:
             self.buf = torch.empty(n, dtype=torch.bfloat16, device=device)
         return self.buf[:n].view(rows, cols)
 
+    def tensors(self):
+        return [] if self.buf is None else [self.buf]
+
 
 class Q4Matrix:
     """A (possibly row-packed) quantised weight as the layer forward consumes it: codes,
@@ -92,6 +95,9 @@ class Q4Matrix:
                 if bias is not None:
                     c2 += bias.float()
                 self.c2 = c2.contiguous()
+
+    def tensors(self):
+        return [t for t in (self.codes, self.absmax, self.bias, self.gamma, self.c1, self.c2) if t is not None]
 
     def _expand(self, col_scale, out):
         if self.int8:

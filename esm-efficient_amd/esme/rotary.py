@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from esme import _hip
+from esme.nn import Derived
 
 
 def culen_indices(cu_lens: torch.Tensor) -> torch.Tensor:
@@ -36,6 +37,7 @@ class RotaryEmbedding(nn.Module):
         # tables `pad_to` wide for a head-padded layout: the real halves sit pad_to/2 apart, pad slots get
         # cos = 1, sin = 0 (esme.attention.head_slots)
         self.pad_to = pad_to if pad_to and pad_to != dim else None
+        self._derived = Derived()          # dtype -> (cos, sin)
         self._seq_len_cached = 0
         self._cos_cached: Optional[torch.Tensor] = None
         self._sin_cached: Optional[torch.Tensor] = None
@@ -47,25 +49,28 @@ class RotaryEmbedding(nn.Module):
         """Tables are built on the host in fp32 and rounded to `dtype` exactly as the
         reference does on its device (rotary.py:116-149), then uploaded once.  One cached pair per dtype (precision 'half' may need
         float16 tables for some layers and float32 tables for others in the same forward); `_cos_cached` / `_sin_cached` are the
-        pair requested last."""
-        cache = self.__dict__.setdefault('_table_cache', {})
-        hit = cache.get(dtype)
-        if hit is None or seqlen > hit[2] or hit[0].device != torch.device(device):
-            seqlen = max(seqlen, hit[2] if hit is not None else 0, self._seq_len_cached)
-            t = torch.arange(seqlen, dtype=torch.float32)
-            ang = torch.outer(t, self._compute_inv_freq())
-            ang = torch.cat((ang, ang), dim=-1)
-            cos, sin = ang.cos().to(dtype), ang.sin().to(dtype)
-            if self.pad_to is not None:
-                h, hp = self.dim // 2, self.pad_to // 2
-                pc, ps = torch.ones(seqlen, self.pad_to, dtype=dtype), torch.zeros(seqlen, self.pad_to, dtype=dtype)
-                for src, dst in ((0, 0), (h, hp)):
-                    pc[:, dst:dst + h] = cos[:, src:src + h]
-                    ps[:, dst:dst + h] = sin[:, src:src + h]
-                cos, sin = pc, ps
-            hit = cache[dtype] = (cos.to(device), sin.to(device), seqlen)
-            self._seq_len_cached = max(self._seq_len_cached, seqlen)
-        self._cos_cached, self._sin_cached = hit[0], hit[1]
+        pair requested last.  The entry's key is (length, device) of the pair it holds; a pair is replaced only by a longer one or one on
+        another device, so the length check stands here, in front of Derived.get's comparison for equality."""
+        device = torch.device(device)
+        key = self._derived.key(dtype)
+        if key is None or seqlen > key[0] or key[1] != device:
+            key = (max(seqlen, key[0] if key is not None else 0, self._seq_len_cached), device)
+        self._cos_cached, self._sin_cached = self._derived.get(dtype, key, self._build_tables, key[0], device, dtype)
+        self._seq_len_cached = max(self._seq_len_cached, key[0])
+
+    def _build_tables(self, seqlen: int, device, dtype):
+        t = torch.arange(seqlen, dtype=torch.float32)
+        ang = torch.outer(t, self._compute_inv_freq())
+        ang = torch.cat((ang, ang), dim=-1)
+        cos, sin = ang.cos().to(dtype), ang.sin().to(dtype)
+        if self.pad_to is not None:
+            h, hp = self.dim // 2, self.pad_to // 2
+            pc, ps = torch.ones(seqlen, self.pad_to, dtype=dtype), torch.zeros(seqlen, self.pad_to, dtype=dtype)
+            for src, dst in ((0, 0), (h, hp)):
+                pc[:, dst:dst + h] = cos[:, src:src + h]
+                ps[:, dst:dst + h] = sin[:, src:src + h]
+            cos, sin = pc, ps
+        return cos.to(device), sin.to(device)
 
     def tables(self, max_len: int, device, dtype=torch.bfloat16) -> Tuple[torch.Tensor, torch.Tensor]:
         self._update_cos_sin_cache(max_len, device, dtype)

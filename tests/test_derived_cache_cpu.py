@@ -1,4 +1,5 @@
-"""Every derived weight copy of the transformer block is reported by esme.graph.external_tensors (no device: the builders are plain torch ops).
+"""Every derived tensor -- the transformer block's weight copies, the padded embedding table and head weights, rotary tables, LoRA's stage
+form -- is reported by esme.graph.external_tensors (no device: the builders are plain torch ops).
 
 A captured hipGraph reads these copies through raw pointers and keeps alive only what external_tensors() lists, so a copy missing from it
 can be freed under a live graph.  Each form the block can hand to a kernel -- plain, LayerNorm-folded, fp16, fp16 with an extension
@@ -109,3 +110,48 @@ def test_lora_weight_forms_are_reported_and_follow_an_edit(kind):
         p.data.normal_()                                  # (lora_B starts at zero)
     check_reported_and_rebuilt(model, lora_forms(model))
     check_reported_and_rebuilt(model, weight_forms(model))          # the base forms, read through the adapter wrappers
+
+
+def test_padded_embedding_table_and_lm_head_are_reported_and_follow_an_edit():
+    model = build('esm2_padded')
+    check_reported_and_rebuilt(model, {'embed table': model._embed_table, 'lm head padded': model.lm_head._padded_weights})
+
+
+def test_rotary_tables_of_every_dtype_are_reported_and_regrow_alone():
+    model = build('esm2')
+    rot = model.layers[0].self_attn.rot_emb
+    pairs = {dt: rot.tables(90, 'cpu', dt) for dt in (torch.bfloat16, torch.float16, torch.float32)}
+    ptrs = {dt: {t.data_ptr() for t in pair} for dt, pair in pairs.items()}
+    assert all(p <= reported(model) for p in ptrs.values())          # all three at once
+    cos, sin = rot.tables(410, 'cpu', torch.bfloat16)
+    assert cos.shape[0] >= 410 and {cos.data_ptr(), sin.data_ptr()} <= reported(model)
+    assert not (ptrs[torch.bfloat16] & reported(model)), 'the replaced bf16 pair is still reported'
+    assert rot._cos_cached is cos and rot._sin_cached is sin
+    for dt in (torch.float16, torch.float32):                       # untouched: same addresses, still reported
+        assert {t.data_ptr() for t in rot.tables(90, 'cpu', dt)} == ptrs[dt] <= reported(model)
+        assert rot._cos_cached.dtype == dt                          # the pair asked for last
+
+
+def test_lora_stage_form_is_reported_and_follows_an_edit():
+    model = build('esm2')
+    model.add_lora(rank=8, alpha=8, layers=('query', 'value', 'output'), adapter_names=['a', 'b'])
+    for p in model.parameters():
+        p.data.normal_()
+    q = model.layers[0].self_attn.q
+    check_reported_and_rebuilt(model, {f'stage form names={names}': lambda names=names: q.stage_form(names) for names in (None, ['b'])})
+
+
+def test_cls_head_padded_weight_is_reported_and_follows_an_in_place_write():
+    from esme.head import ClsHead
+    torch.manual_seed(0)
+    head = ClsHead(120, num_cls=2, hidden_dim=64).eval()
+    lin = head.head[0]
+    w = head._mlp._weight(lin, 128)
+    assert w.shape == (64, 128) and w.data_ptr() != lin.weight.data_ptr() and torch.equal(w[:, :120], lin.weight.data) and not w[:, 120:].any()
+    assert w.data_ptr() in reported(head)
+    assert head._mlp._weight(lin, 128) is w
+    with torch.no_grad():
+        lin.weight.copy_(torch.randn_like(lin.weight))
+    w2 = head._mlp._weight(lin, 128)
+    assert w2 is not w and torch.equal(w2[:, :120], lin.weight.data)
+    assert w2.data_ptr() in reported(head) and w.data_ptr() not in reported(head)

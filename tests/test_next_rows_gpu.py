@@ -27,11 +27,11 @@ DEV = 'cuda:0'
 FASTA = os.path.join(GOLDEN, 'data', 'test.fa')
 
 
-def build_q4(kind, L, E, H, seed):
+def build_q4(kind, L, E, H, seed, quantization='4bit'):
     from esme import ESM
     with tempfile.TemporaryDirectory() as td:
         path = syn.write_checkpoint(os.path.join(td, 'm.safetensors'), f'{kind}_test', L, E, H, seed=seed)
-        return ESM.from_pretrained(path, quantization='4bit', device=DEV)
+        return ESM.from_pretrained(path, quantization=quantization, device=DEV)
 
 
 def spearman(a, b):
@@ -298,6 +298,27 @@ def test_graph_replay_equals_eager():
     lens = [7, 33, 50]
     tk, c3 = syn.random_tokens(lens, seed=3).to(DEV), syn.cu_lens_of(lens).to(DEV)
     assert torch.equal(q4.graphed(tk, (c3, 50)), q4(tk, (c3, 50)))
+
+
+@pytest.mark.parametrize('kind,L,E,H,seed,quantization', [('esmc', 2, 128, 2, 21, '4bit'), ('esm2', 2, 320, 20, 7, '4bit'), ('esm2', 2, 320, 20, 7, '8bit')])
+def test_graph_keeps_quantised_state_alive(kind, L, E, H, seed, quantization):
+    """What a captured graph of a quantised model reads through raw pointers besides parameters -- the expansion scratch, every packed
+    matrix's codes, absmax and LayerNorm-fold constants -- is among external_tensors(model), the list the graph holds references to."""
+    from esme.graph import external_tensors
+    model = build_q4(kind, L, E, H, seed, quantization)
+    lens = [7, 33, 50]
+    tk, c3 = syn.random_tokens(lens, seed=3).to(DEV), syn.cu_lens_of(lens).to(DEV)
+    eager = model(tk, (c3, 50))
+    assert torch.equal(model.graphed(tk, (c3, 50)), eager)
+    kept = {t.data_ptr() for t in external_tensors(model)}
+    assert model._q4_scratch.buf.data_ptr() in kept, 'the scratch buffer is not reported'
+    for i, layer in enumerate(model.layers):
+        att = layer.self_attn
+        for name, m in (('qkv', att._q4_qkv), ('out', att._q4_out), ('up', layer._q4_up), ('down', layer._q4_down)):
+            for field in ('codes', 'absmax', 'gamma', 'c1', 'c2'):
+                t = getattr(m, field)
+                assert t is None or t.data_ptr() in kept, f'layer {i} {name}.{field} is not reported'
+            assert (m.gamma is None) == (name in ('out', 'down')) and m.codes is not None and m.absmax is not None
 
 
 def test_mask_margin_graph_path_equals_eager():
