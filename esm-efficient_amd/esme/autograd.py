@@ -13,6 +13,10 @@
  - `TokenEmbedding`: the token-embedding lookup of a model that opted in with mark_trainable(embedding=True): forward =
    esme_hip_embed, backward = esme_hip_embed_bwd (include/esme_hip_embed_bwd.h): per table row the fp32 sum of its rows of dX in a fixed
    order, without atomics.
+ - `PositionEmbedding`: the token + learned-position lookup of an ESM-1b / ESM-1v model that opted in with
+   mark_trainable(positions=...): forward = esme_hip_embed_positions on packed ids, backward = esme_hip_embed_bwd for the token table
+   and esme_hip_embed_positions_bwd (include/esme_hip_embed_positions_bwd.h) for the position table: per table row the fp32 sum over
+   the sequences in ascending order, without atomics.
 
  - `AttentionPooling`: forward = esme_hip_attn_pool on the folded queries U, backward = esme_hip_attn_pool_bwd
    (include/esme_hip_attn_pool_bwd.h); `pool_fold` is the fold itself in fp32 torch ops, so that autograd carries dU on to the class
@@ -30,7 +34,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_gemm_wgrad, _hip_segment_mean_bwd
+from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_embed_positions_bwd, _hip_gemm_wgrad, _hip_segment_mean_bwd
 from esme.nn import weight_t
 
 
@@ -78,6 +82,33 @@ class TokenEmbedding(torch.autograd.Function):
         tokens, = ctx.saved_tensors
         V, mask_idx, pad_idx = ctx.args
         return _hip_embed_bwd.embed_bwd(_kernel_rows(d_x), tokens, V, mask_idx, pad_idx), None, None, None
+
+
+class PositionEmbedding(torch.autograd.Function):
+    """x (T, E) = table[tokens] (zero rows for `mask_idx` and for ids outside the table) + pos_table[in-sequence position + pos_offset]
+    for packed int64 ids (T,) and the sequences of `cu_lens` (int32), the sum rounded to bfloat16 once: the bits of the inference
+    embedding of the same rows.  Differentiable in `table` (V, E) and `pos_table` (P, E), both bfloat16; the two addends share one
+    gradient, so d_x feeds both backward kernels unchanged, each only where its table takes a gradient."""
+
+    @staticmethod
+    def forward(ctx, table, pos_table, tokens, cu_lens, max_len, mask_idx, pos_offset):
+        tokens = tokens.contiguous()
+        if cu_lens.dtype != torch.int32:
+            cu_lens = cu_lens.to(torch.int32)
+        cu_lens = cu_lens.contiguous()
+        ctx.save_for_backward(tokens, cu_lens)
+        ctx.args = (table.shape[0], pos_table.shape[0], int(max_len), int(mask_idx), int(pos_offset))
+        pos, _ = _hip.seq_positions(cu_lens, tokens.numel())
+        return _hip.embed_positions(tokens, table.detach(), pos_table.detach(), pos, int(pos_offset), mask_idx=int(mask_idx))
+
+    @staticmethod
+    def backward(ctx, d_x):
+        tokens, cu_lens = ctx.saved_tensors
+        V, P, max_len, mask_idx, pos_offset = ctx.args
+        d_x = _kernel_rows(d_x)
+        d_table = _hip_embed_bwd.embed_bwd(d_x, tokens, V, mask_idx, -1) if ctx.needs_input_grad[0] else None
+        d_pos = _hip_embed_positions_bwd.embed_positions_bwd(d_x, cu_lens, P, pos_offset, max_len) if ctx.needs_input_grad[1] else None
+        return d_table, d_pos, None, None, None, None, None
 
 
 class FrozenLinear(torch.autograd.Function):

@@ -763,8 +763,11 @@ class ESM2(nn.Module):
         dropout).  `model.train(); model(...)` still raises: the fused inference forward has no backward.  NotImplementedError, by
         name, for a precision other than 'fast', quantised weights (unless add_lora(quantized_base=True) opted in: then the adapters
         and the LM head train over the quantised base, and a LayerNorm that requires grad is refused), the padded ESM2-35M layout, dropout > 0, a head dim outside
-        {32, 64}, the learned-position ESM-1 models and a token embedding that requires grad without mark_trainable(embedding=True)
-        (with it the table trains: esme.autograd.TokenEmbedding; quantised models stay refused).
+        {32, 64}, the learned-position ESM-1 models without mark_trainable(positions=...) and a token embedding that requires grad
+        without mark_trainable(embedding=True) (with it the table trains: esme.autograd.TokenEmbedding; quantised models stay refused).
+        ESM-1b / ESM-1v after mark_trainable(positions=True or 'frozen'): the ids are packed, the lookup is
+        esme.autograd.PositionEmbedding (the position table's gradient is esme_hip_embed_positions_bwd), ESM-1b's emb_layer_norm_before
+        follows in torch ops, then the same layers; a max_len above the position table raises ValueError before any launch.
         `layers=[...]` (with logits=False; ValueError with logits=True, the LM head takes E columns) taps the raw outputs of those
         layers as forward_representation(layers=) does -- the same check of the indices, the same order (that of the model's layers)
         -- and concatenates them after the final-LayerNorm output on the feature axis: (T, (1 + k) E) / (B, S, (1 + k) E), every
@@ -781,7 +784,14 @@ class ESM2(nn.Module):
                   f'quantised weights have no backward (load the model without quantization=; {ag.QLORA_HINT})')
         ag.check_frozen_norms((('emb_layer_norm_after', self.emb_layer_norm_after),), qlora)
         ag.refuse(self.padded, 'the padded layout (ESM2-35M: head dim 24, a width that is not a multiple of 64) has no backward')
-        ag.refuse(type(self)._embedding_phys is not ESM2._embedding_phys, 'the learned-position models (ESM-1b / ESM-1v) are not covered')
+        learned = type(self)._embedding_phys is not ESM2._embedding_phys
+        train_pos = self.__dict__.get('_train_positions', False) if learned else False
+        ag.refuse(learned and not train_pos, 'the learned-position models (ESM-1b / ESM-1v) are not covered')
+        ag.refuse(learned and getattr(self, 'quantization', None) is not None,
+                  'the learned-position models (ESM-1b / ESM-1v) do not train over quantised weights, with or without adapters')
+        norm_before = getattr(self, 'emb_layer_norm_before', None) if learned else None
+        if norm_before is not None:
+            ag.check_frozen_norms((('emb_layer_norm_before', norm_before),), qlora)
         ag.refuse(train_emb and getattr(self, 'quantization', None) is not None,
                   'mark_trainable(embedding=True) on a quantised model: over a quantised base only the adapters and the LM head train')
         for layer in self.layers:
@@ -804,7 +814,25 @@ class ESM2(nn.Module):
                 cu_lens, max_len = pad_args
             else:
                 assert tokens.ndim == 2, 'tokens are expected to be padded with shape (batch, seq_len, embed_dim)'
-            if train_emb:
+            if learned:
+                # packed BEFORE the lookup, like the trainable token table below: the index of a kept row in the position table is its
+                # in-sequence position + padding_idx + 1 for packed and for 2-D tokens (positions() counts the tokens that are no `<pad>`)
+                pe = self.embed_positions
+                limit = int(max_len) if pad_args is not None else tokens.shape[1]
+                if limit > pe.max_positions:
+                    raise ValueError(f'Sequence length {limit} above maximum  sequence length of {pe.max_positions}')
+                if self.debug_checks:
+                    self.check_tokens(tokens)
+                if pad_args is None:
+                    pad_indices, cu_lens, max_len = self._unpad_index(tokens)
+                    tokens_packed = tokens.flatten()[pad_indices]
+                else:
+                    tokens_packed = tokens
+                x = ag.PositionEmbedding.apply(self.embed_tokens.weight, pe.weight, tokens_packed, cu_lens, int(max_len),
+                                               self.alphabet.mask_idx, pe.padding_idx + 1)
+                if norm_before is not None:
+                    x = ag.layer_norm(x, norm_before)
+            elif train_emb:
                 # the ids are packed BEFORE the lookup (the rows that are kept are the same rows): a `<pad>` row never reaches the
                 # lookup, so it contributes nothing to the table's gradient, and 2-D tokens give the packed gradients
                 if self.debug_checks:
@@ -847,7 +875,7 @@ class ESM2(nn.Module):
         return self
 
     # -- full fine-tuning (esme/autograd.py TrainableLinear, include/esme_hip_gemm_wgrad.h) --------------------------------------
-    def mark_trainable(self, projections=True, norms=True, layers=None, embedding=False):
+    def mark_trainable(self, projections=True, norms=True, layers=None, embedding=False, positions=False):
         """Select what full fine-tuning trains through `forward_trainable`.  `projections`: requires_grad on the weights and biases of
         the selected layers' own projections (q, k, v, out, FFN up / down, SwiGLU's two; under a LoRA wrapper the base `layer`) --
         their gradients come from esme_hip_gemm_wgrad.  `norms`: on the selected layers' LayerNorms (ESM-C's q / k norms included) and,
@@ -857,10 +885,26 @@ class ESM2(nn.Module):
         (masked-LM training): requires_grad on `embed_tokens.weight`, and `forward_trainable` then runs the lookup as
         esme.autograd.TokenEmbedding, whose backward is esme_hip_embed_bwd.  `embedding=False` (the default) withdraws the opt-in, and
         clears the flag where the opt-in had set it; a flag set by hand is not touched, and `forward_trainable` keeps refusing it.  The
-        LM head and LoRA adapters keep their flags (mark_lmhead, mark_only_lora_as_trainable)."""
+        LM head and LoRA adapters keep their flags (mark_lmhead, mark_only_lora_as_trainable).
+        `positions` is the opt-in of the learned-position models (ESM-1b / ESM-1v), which `forward_trainable` refuses without it:
+        True sets requires_grad on `embed_positions.weight` (its gradient is esme_hip_embed_positions_bwd; with
+        `mark_trainable(False, False, positions=True)` the table trains alone, the run that made the 4 096-position checkpoints);
+        'frozen' opts in and leaves the table frozen (LoRA, task-head or top-layer fine-tuning of these models); False (the default)
+        withdraws the opt-in and clears a flag the opt-in had set.  With `norms` and `layers=None`, ESM-1b's `emb_layer_norm_before` is
+        trained like `emb_layer_norm_after`.  ValueError for a truthy `positions` on a model without a position table."""
         from esme.lora import LoRA
         if embedding and getattr(self, 'quantization', None) is not None:
             raise NotImplementedError('mark_trainable(embedding=True): the token embedding does not train on a quantised model')
+        if positions not in (False, True, 'frozen'):
+            raise ValueError(f"mark_trainable: positions must be False, True or 'frozen', got {positions!r}")
+        if positions != 'frozen':
+            positions = bool(positions)
+        pe = getattr(self, 'embed_positions', None)
+        if positions and pe is None:
+            raise ValueError(f'mark_trainable(positions={positions!r}): {type(self).__name__} has no embed_positions table '
+                             '(only the learned-position models ESM-1b / ESM-1v do)')
+        if positions and getattr(self, 'quantization', None) is not None:
+            raise NotImplementedError(f'mark_trainable(positions={positions!r}): the learned-position models do not train on a quantised model')
         L = len(self.layers)
         if layers is None:
             chosen = set(range(L))
@@ -890,14 +934,27 @@ class ESM2(nn.Module):
             for ln in lns:
                 for p in ln.parameters(recurse=False):
                     p.requires_grad_(bool(norms) and i in chosen)
-        for p in self.emb_layer_norm_after.parameters(recurse=False):
-            p.requires_grad_(bool(norms) and layers is None)
+        for ln in (self.emb_layer_norm_after, getattr(self, 'emb_layer_norm_before', None)):
+            if ln is not None:
+                for p in ln.parameters(recurse=False):
+                    p.requires_grad_(bool(norms) and layers is None)
         if embedding:
             self.__dict__['_train_embedding'] = True
             self.embed_tokens.weight.requires_grad_(True)
         elif self.__dict__.pop('_train_embedding', False):
             self.embed_tokens.weight.requires_grad_(False)
+        was = self.__dict__.pop('_train_positions', False)
+        if positions:
+            self.__dict__['_train_positions'] = positions
+        if positions is True:
+            pe.weight.requires_grad_(True)
+        elif was is True:                                           # (the flag the opt-in had set; one set by hand is not touched)
+            pe.weight.requires_grad_(False)
         return self
+
+    def extend_positions(self, max_positions: int):
+        """Only the learned-position models (ESM-1b / ESM-1v) have a position table to extend."""
+        raise ValueError(f'extend_positions: {type(self).__name__} has no embed_positions table')
 
     # -- loading -------------------------------------------------------------------
     @classmethod
@@ -999,6 +1056,28 @@ class _LearnedPositionESM(ESM2):
             x.masked_fill_(tokens.eq(self.alphabet.padding_idx).unsqueeze(-1), 0.0)   # row selection, no arithmetic
         return x
 
+    def extend_positions(self, max_positions: int):
+        """Replace `embed_positions` by a table for sequences of up to `max_positions` tokens: a new LearnedPositionalEmbedding of the
+        same dtype and device whose first rows are the old table, bit for bit, and whose other rows are zeros -- how the run that made
+        the 4 096-position checkpoints started from the released 1 024-position tables; train the new rows with
+        mark_trainable(False, False, positions=True).  requires_grad is carried over; captured graphs, the C-entry descriptor and
+        every derived weight copy are dropped, since they hold the old table.  ValueError when the table would shrink.  Returns self."""
+        old = self.embed_positions
+        max_positions = int(max_positions)
+        if max_positions < old.max_positions:
+            raise ValueError(f'extend_positions: cannot shrink the position table from {old.max_positions} to {max_positions} positions')
+        if max_positions == old.max_positions:
+            return self
+        w = old.weight
+        with torch.device(w.device):
+            new = LearnedPositionalEmbedding(max_positions, old.embedding_dim, dtype=w.dtype)
+        with torch.no_grad():
+            new.weight[:old.num_embeddings].copy_(w)
+        new.weight.requires_grad_(w.requires_grad)
+        self.embed_positions = new.train(self.training)
+        self.invalidate_graphs()
+        return self
+
     def _embedding_exact(self, x, tokens, pad_args, pad_indices):
         """token row + learned-position row summed in fp32 [-> emb_layer_norm_before in fp32 (ESM-1b)] -> `<pad>` rows zeroed: what
         the reference's fp32 forward starts from (the bf16 path rounds the sum, and ESM-1b's LayerNorm output, to bf16)."""
@@ -1025,9 +1104,15 @@ class _LearnedPositionESM(ESM2):
         assert name == cls.__name__.lower(), \
             f'Invalid weight for the {cls.__name__} model. ' \
             f'You are trying to load a {name} model weights to a {cls.__name__} model.'
+        from safetensors import safe_open
+        with safe_open(path, framework='pt', device='cpu') as f:      # a table written after extend_positions() has more rows
+            rows = f.get_slice('embed_positions.weight').get_shape()[0]
         with torch.device('meta'):
-            return cls(checkpointing=checkpointing, num_layers=int(md.get('num_layers', 33)),
-                       embed_dim=int(md.get('embed_dim', 1280)), attention_heads=int(md.get('attention_heads', 20)))
+            model = cls(checkpointing=checkpointing, num_layers=int(md.get('num_layers', 33)),
+                        embed_dim=int(md.get('embed_dim', 1280)), attention_heads=int(md.get('attention_heads', 20)))
+            if rows != model.embed_positions.num_embeddings:
+                model.embed_positions = LearnedPositionalEmbedding(rows - 2, model.embed_dim, dtype=model.embed_positions.weight.dtype)
+        return model
 
 
 class ESM1b(_LearnedPositionESM):
