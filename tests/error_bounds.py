@@ -180,8 +180,12 @@ def swiglu_reference(a, wa, wf, out_fmt='bf16'):
     (relative ln2 * 2^-24 |log2(e) gate| = 2^-24 |gate| on the exponential), v_exp_f32, the add of 1, v_rcp_f32, two products.  The
     input errors propagate through |d silu / d gate| <= 1.1 and |silu(gate)|."""
     a64 = a.double()
-    g, f = a64 @ wa.double().T, a64 @ wf.double().T
-    dg, df = dot_term(a64, wa), dot_term(a64, wf)
+    return swiglu_bound(a64 @ wa.double().T, a64 @ wf.double().T, dot_term(a64, wa), dot_term(a64, wf), out_fmt)
+
+
+def swiglu_bound(g, f, dg, df, out_fmt='bf16'):
+    """The SwiGLU epilogue of swiglu_reference on gate / fc values g, f (float64) that carry the pre-epilogue bounds dg, df: the plain GEMM's
+    dot terms, or the LayerNorm-folded projection's `pre` (ln_fold_reference).  Returns (val, bound, pre)."""
     sig = torch.sigmoid(g)
     silu = g * sig
     val = silu * f

@@ -13,57 +13,25 @@ import pytest
 import torch
 
 import error_bounds as eb
+import gemm_operands as ops
+from gemm_operands import BF, BIAS_MIN_ELEMENTS, DEV, H16, rnd
 from oracle import esm_oracle as O
 from esme import _hip
 from esme import synthetic as syn
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-BF = torch.bfloat16
-H16 = torch.float16
 LOG2E = 1.4426950408889634
-MARGINS = {}
-USED = {}
-BIASES = {}
-
-
-def record(family, ratio, used=None):
-    """Keep the worst err / bound per family and, where the recipe's pre-rounding part is given, the share of it used
-    (eb.budget_used: what is left once an element on a rounding tie is set aside)."""
-    MARGINS[family] = max(MARGINS.get(family, 0.0), ratio)
-    if used is not None:
-        USED[family] = max(USED.get(family, 0.0), used)
-    return ratio
-
-
-def record_bias(kernel, got, ref, pre, fmt, need=10 ** 5):
-    """|rounding bias| < 0.05 ulp over at least `need` elements whose pre-rounding bound is under 0.05 ulp.  Fewer such elements is a
-    failure, not a skip: call it only where the shape and the recipe leave enough of them (the call sites say which)."""
-    bias, n = eb.rounding_bias(got, ref, pre, fmt)
-    assert n >= need, f'{kernel}: only {n} elements qualify for the rounding-bias check (need {need})'
-    prev = BIASES.get(kernel)
-    BIASES[kernel] = bias if prev is None or abs(bias) > abs(prev[0]) else prev[0], n
-    assert abs(bias) < 0.05, f'{kernel}: rounding bias {bias:+.3f} ulp over {n} elements (round to nearest gives ~0)'
-    return bias, n
-
-
-BIAS_MIN_ELEMENTS = 3 * 10 ** 5          # outputs this large leave >= 10^5 elements under the 0.05-ulp filter in every recipe below
+LEDGER = ops.Ledger('error bounds')
+record, record_bias = LEDGER.record, LEDGER.record_bias
+# `persist` below: under 2 * (compute units & ~7) tiles of 256 x 256 (512 on an MI355X; the largest GEMM here has 85) option 1 runs the
+# per-tile kernel, the same launch as option 0 (tests/gemm_path.py); the persistent kernel is held to these bounds in
+# tests/test_gemm_persistent_bounds_gpu.py.
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _report():
     yield
-    print('\n[error bounds] worst err / bound per kernel family:')
-    for k in sorted(MARGINS):
-        print(f'  {k:40s} {MARGINS[k]:.3f}' + (f'   pre-rounding budget used {USED[k]:.3f}' if k in USED else ''))
-    print('[error bounds] rounding bias (ulp) per kernel:')
-    for k in sorted(BIASES):
-        print(f'  {k:40s} {BIASES[k][0]:+.4f}  (n = {BIASES[k][1]})')
-
-
-def rnd(shape, seed, scale=1.0, dtype=BF, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale + offset).to(dtype).to(DEV)
+    LEDGER.report()
 
 
 def cu_of(lengths):
@@ -79,8 +47,7 @@ GEMM_SHAPES = [(1, 320, 64), (255, 33, 5120), (257, 1280, 64), (4099, 384, 5120)
 @pytest.mark.parametrize('tile', [1, 2])
 @pytest.mark.parametrize('persist', [0, 1])
 def test_gemm_plain_epilogues(M, N, K, tile, persist):
-    a, w, b = rnd((M, K), M + K), rnd((N, K), N + K, 1 / math.sqrt(K)), rnd((N,), N, 0.5)
-    r = rnd((M, N), 3 + M)
+    a, w, b, r = ops.plain_operands(M, N, K)
     lay = eb.gemm_layout(128 * tile, 128 * tile)
     with _hip.gemm_options(tile=tile, persist=persist):
         for epi, bias in (('none', b), ('none', None), ('gelu', b), ('residual', b)):
@@ -94,7 +61,7 @@ def test_gemm_plain_epilogues(M, N, K, tile, persist):
         if N % 64 == 0:
             F = N // 2
             wa, wf = w[:F], w[F:]
-            packed = torch.cat((wa.view(F // 32, 1, 32, K), wf.view(F // 32, 1, 32, K)), 1).reshape(2 * F, K).contiguous()
+            packed = ops.swiglu_pack(wa, wf)
             got = _hip.gemm(a, packed, None, _hip.EPI_SWIGLU)
             ref, bound, pre = eb.swiglu_reference(a, wa, wf)
             record('gemm bf16 swiglu', eb.assert_bounded(got, ref, bound, f'gemm swiglu {M}x{N}x{K} tile{tile} persist{persist}', lay),
@@ -103,29 +70,12 @@ def test_gemm_plain_epilogues(M, N, K, tile, persist):
                 record_bias('gemm bf16 swiglu', got, ref, pre, 'bf16')
 
 
-def _ln_fold_operands(T, E, N, seed, kind):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(T, E, generator=g) * 1.5
-    if kind == 'dc20':
-        x = x + 20.0
-    elif kind == 'outlier':
-        x[:, 7] *= 60.0
-    gamma = (1 + 0.1 * torch.randn(E, generator=g)).to(BF)
-    beta = (0.05 * torch.randn(E, generator=g)).to(BF)
-    w = (torch.randn(N, E, generator=g) * E ** -0.5).to(BF)
-    b = (0.1 * torch.randn(N, generator=g)).to(BF)
-    wprime = (w.double() * gamma.double()).to(BF)
-    c1 = wprime.double().sum(1).float()
-    c2 = (w.double() @ beta.double() + b.double()).float()
-    return x.to(BF).to(DEV), wprime.to(DEV), c1.to(DEV), c2.to(DEV)
-
-
 @pytest.mark.parametrize('kind', ['plain', 'dc20', 'outlier'])
 @pytest.mark.parametrize('tile', [1, 2])
 @pytest.mark.parametrize('persist', [0, 1])
 def test_gemm_layernorm_fold(kind, tile, persist):
     T, E, N = 1000, 640, 1280
-    x, wp, c1, c2 = _ln_fold_operands(T, E, N, 5 + len(kind), kind)
+    x, wp, c1, c2 = ops.ln_fold_operands(T, E, N, 5 + len(kind), kind)
     sums = _hip.row_sums(x)
     with _hip.gemm_options(tile=tile, persist=persist):
         got = _hip.gemm_fused(x, wp, None, ln=(sums, E, 1e-5, c1, c2))
@@ -173,9 +123,7 @@ def test_gemm_fused_rotary(d, H, q_scale, tile, persist):
 @pytest.mark.parametrize('tile', [1, 2])
 @pytest.mark.parametrize('persist', [0, 1])
 def test_gemm_residual_stats_and_fp32_stream(M, N, K, tile, persist):
-    a, w, b = rnd((M, K), 60), rnd((N, K), 61, 1 / math.sqrt(K)), rnd((N,), 62, 0.5)
-    r = rnd((M, N), 63)
-    x32 = (torch.randn(M, N, generator=torch.Generator().manual_seed(64)) * 2).to(DEV)
+    a, w, b, r, x32 = ops.residual_stream_operands(M, N, K)
     with _hip.gemm_options(tile=tile, persist=persist):
         nblk = _hip.stats_blocks(M, N)
         stats = torch.empty(nblk, M, 2, dtype=torch.float32, device=DEV)
@@ -185,11 +133,8 @@ def test_gemm_residual_stats_and_fp32_stream(M, N, K, tile, persist):
     ref, bound, _ = eb.gemm_reference(a, w, b, 'residual', resid=r, alpha=0.5)
     record('gemm bf16 residual', eb.assert_bounded(got, ref, bound, f'residual {M}x{N}x{K} tile{tile} persist{persist}'))
     # stats_out: per row {sum, sum of squares} of the ROUNDED outputs, fp32 partials per column block
-    o = got.double()
-    s_ref = torch.stack((o.sum(1), (o * o).sum(1)), 1)
+    s_ref, sb = ops.stats_reference(got, nblk)
     st = stats.double().sum(0)
-    sb = torch.stack((eb.C_DOT * eb.U32 * math.sqrt(N) * torch.sqrt((o * o).sum(1)) + nblk * eb.U32 * o.abs().sum(1),
-                      eb.C_DOT * eb.U32 * math.sqrt(N) * torch.sqrt((o ** 4).sum(1)) + (nblk + 1) * eb.U32 * (o * o).sum(1)), 1)
     record('gemm stats_out', eb.assert_bounded(st, s_ref, sb, 'stats_out'))
     # fp32 residual stream: x32 <- fma(alpha, acc + bias, x32) (gemm.hip:952, gemm_bf16_kernel), one rounding; x16 = its bf16 rounding, bit for bit
     y, _, pre = eb.gemm_reference(a, w, b)
@@ -204,9 +149,7 @@ def test_gemm_residual_stats_and_fp32_stream(M, N, K, tile, persist):
 @pytest.mark.parametrize('persist', [0, 1])
 def test_gemm_f16(M, N, K, tile, persist):
     """Precision 'half': fp16 operands and output; the pair stream (scaled, with the extension K-tile)."""
-    a = rnd((M, K), 70, dtype=H16)
-    w = rnd((N, K), 71, 1 / math.sqrt(K)).to(H16)               # bf16 weights converted to fp16 (exact)
-    b = rnd((N,), 72, 0.5)
+    a, w, b = ops.f16_operands(M, N, K)
     with _hip.gemm_options(tile=tile, persist=persist):
         got = _hip.gemm_fused(a, w, b)
         gel = _hip.gemm_fused(a, w, b, _hip.EPI_GELU)
@@ -252,21 +195,11 @@ def test_gemm_f16_ln_fold_extension_tile_and_rotary(form, tile, persist):
     T, E = sum(lengths), H * d
     cu = cu_of(lengths)
     pos, _ = _hip.seq_positions(cu, T)
-    g = torch.Generator().manual_seed(90 + len(form))
-    x32 = torch.randn(T, E, generator=g) * 1.5
     sel = torch.tensor([5, 77, 300], dtype=torch.int32)
-    x32[:, sel.long()] *= 200.0
-    gamma = (1 + 0.1 * torch.randn(E, generator=g)).to(BF)
-    beta = (0.05 * torch.randn(E, generator=g)).to(BF)
-    w = (torch.randn(3 * E, E, generator=g) * E ** -0.5).to(BF)
-    b = (0.1 * torch.randn(3 * E, generator=g)).to(BF)
-    wp = (w.double() * gamma.double()).to(H16)
-    wext = torch.cat((wp, wp[:, sel.long()], torch.zeros(3 * E, 64 - len(sel), dtype=H16)), 1).contiguous().to(DEV)
-    c1 = wp.double().sum(1).float().to(DEV)
-    c2 = (w.double() @ beta.double() + b.double()).float().to(DEV)
+    x32, _, wext, c1, c2 = (t.to(DEV) for t in ops.f16_ln_fold_operands(T, E, 3 * E, 90 + len(form), sel))
     pair = torch.zeros(T, 2 * E + 64, dtype=H16, device=DEV)
     sums = torch.empty(1, T, 2, dtype=torch.float32, device=DEV)
-    _hip.stream_operand(x32.to(DEV), pair, sums, pair=True, ext_sel=sel.to(DEV))
+    _hip.stream_operand(x32, pair, sums, pair=True, ext_sel=sel.to(DEV))
     A = pair[:, :E + 64]
     qs = 0.125 * LOG2E if form == 'single_q_scale' else 0.0
     sumsq = torch.zeros(2, H, dtype=torch.int32, device=DEV)
@@ -335,13 +268,14 @@ RASTERS = [(0, 0), (1, 1), (3, 4), (5, 7), (64, 1), (2, 64)]
 def test_gemm_options_bit_equal(family):
     """tile x raster (gm, gn) x persist: groups that do not divide tiles_m / tiles_n (M = 1000: 8 / 4 row tiles; N = 1280: 10 / 5
     column tiles) and gm > tiles_m (64) -- every configuration the same bits, stats_out too (within a tile size, whose stats_out
-    layout differs)."""
+    layout differs).  Under 2 * (compute units & ~7) tiles option persist=1 runs the per-tile kernel (tests/gemm_path.py), so at this shape
+    both options are the same launch; the persistent kernel runs these rasters in tests/test_gemm_persistent_bounds_gpu.py."""
     M, N, K = 1000, 1280, 640
     a, w, b = rnd((M, K), 80), rnd((N, K), 81, 1 / math.sqrt(K)), rnd((N,), 82, 0.5)
     r = rnd((M, N), 83)
     outs, stats = {}, {}
     if family == 'ln_fold':
-        x, wp, c1, c2 = _ln_fold_operands(M, K, N, 84, 'plain')
+        x, wp, c1, c2 = ops.ln_fold_operands(M, K, N, 84, 'plain')
         sums = _hip.row_sums(x)
     if family == 'rotary':
         lengths = [1, 300, 64, 635]

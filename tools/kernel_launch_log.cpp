@@ -13,6 +13,7 @@
 //   (attention: -DESME_KLL_ATTN and attn.hip.  --unresolved-symbols: only the __hip_fatbin_<hash> reference of a host-only object.)
 //   ./kll            every case: "== name launches" line, then its log
 //   ./kll --dump C   the log of case C alone (diff it against a build with another gemm.hip / attn.hip)
+//   ./kll --cases F  (GEMM build) the launches of the calls listed in file F, one "form M N K tile persist raster_gm raster_gn device" per line
 #include ESME_SRC
 
 #include <cxxabi.h>
@@ -801,8 +802,43 @@ void cases() {
 
 }  // namespace kll
 
+#ifdef ESME_KLL_GEMM
+// --cases FILE: one call per line, "form M N K tile persist raster_gm raster_gn device" (form: a name of kForms; tile 0 / 1 / 2; persist -1 / 0 / 1;
+// device: the ordinal hipGetDevice answers -- 0, 1, 2 = 256, 4, 300 compute units; '#' opens a comment).  Prints "== line<N> <launches>" and the
+// call's log, as the table's cases are printed.  tests/test_gemm_path_cpu.py pins tests/gemm_path.py (which kernel a call runs) with it.
+static int run_case_file(const char* path) {
+    using namespace kll;
+    FILE* f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    char line[512], form[64];
+    for (int no = 1; fgets(line, sizeof line, f); ++no) {
+        if (line[0] == '#' || line[0] == '\n') continue;
+        ll M;
+        int N, K, t, persist, gm, gn, dev;
+        if (sscanf(line, "%63s %lld %d %d %d %d %d %d %d", form, &M, &N, &K, &t, &persist, &gm, &gn, &dev) != 9 || t < 0 || t > 2 || dev < 0 || dev > 2) {
+            fprintf(stderr, "%s:%d: want 'form M N K tile persist raster_gm raster_gn device'\n", path, no); fclose(f); return 2;
+        }
+        const Form* fm = nullptr;
+        for (const Form& k : kForms) if (!strcmp(k.name, form)) fm = &k;
+        if (!fm) { fprintf(stderr, "%s:%d: no form %s\n", path, no, form); fclose(f); return 2; }
+        g_names.clear(); g_log.clear(); g_launches = 0;
+        esme::error_buffer()[0] = 0;
+        GC c; c.dev = dev; c.M = M; c.N = N; c.K = K; fm->set(c);
+        tile(c, t); c.op.persist = persist; c.op.raster_gm = gm; c.op.raster_gn = gn;
+        call(c);
+        printf("== line%d %d\n", no, g_launches);
+        fputs(g_log.c_str(), stdout);
+    }
+    fclose(f);
+    return 0;
+}
+#endif
+
 int main(int argc, char** argv) {
     using namespace kll;
+#ifdef ESME_KLL_GEMM
+    if (argc == 3 && !strcmp(argv[1], "--cases")) return run_case_file(argv[2]);
+#endif
     const char* only = argc == 3 && !strcmp(argv[1], "--dump") ? argv[2] : nullptr;
     if (argc != 1 && !only) { fprintf(stderr, "usage: %s [--dump CASE]\n", argv[0]); return 2; }
     cases();
