@@ -9,6 +9,11 @@
 // LN(x_t) . A_j DIVIDED by rstd_t, because the LayerNorm-folded GEMM multiplies its whole accumulator by rstd_t afterwards.
 // A has `rank` rows (all adapters and projections of that GEMM stacked); columns rank .. X-1 of u are written as zeros.
 //
+// K range: E is the K of the projection the adapters belong to: the model width (320 .. 2 560) for q / k / v / out and the FFN
+// up-projection, the FFN width F (512 .. 10 240) for the FFN down-projection (x = the first F columns of the (T, F + X) activation
+// buffer, ldx = F + X).  Row offsets (t * ldx, row * E) are 64-bit; k0 + 8 s, the A chunk's ch * 8 and the LDS offsets are ints
+// below E + 64 <= 10 304 and NB * 16 * 72 <= 18 432: nothing depends on E beyond E % 64 == 0.
+//
 // A skinny product (M = T, N = X, K = E) that reads x once.  One workgroup = 4 waves x 32 rows; the A chunk of a 64-wide K step
 // is shared through LDS (144-byte rows: the 16 rows a fragment read touches fall on different banks), x goes global -> register
 // as the MFMA's other operand.  v_mfma_f32_16x16x32_bf16 in transposed form (A rows on the matrix's row side, x rows on the lanes),

@@ -777,6 +777,7 @@ class FlashTransformerLayer(nn.Module):
         self._q4_up = None          # esme.quantization.Q4Matrix pair when the layer is 4-bit
         self._q4_down = None
         self._qlora = False         # set by ESM2.add_lora(quantized_base=True): forward_trainable runs over the quantised FFN projections
+        self._has_lora = False      # set by wrap_ffn_lora: the FFN projections may be esme.lora.LoRA wrappers ('lora' in _derived: _ffn_lora_weights)
 
     def _fold_operands(self):
         ln = self.final[0]
@@ -845,10 +846,171 @@ class FlashTransformerLayer(nn.Module):
                 pad_rows(down.weight.data, self.phys_dim), pad_last(down.bias.data, self.phys_dim) if down.bias is not None else None))
         return down.weight, down.bias
 
-    def _ffn(self, x, alpha, stream, x_stats=None, stats_out=None, ovf=None):
-        """FFN branch onto the residual stream `stream` (ForwardContext.residual(...), or {'resid': ..., 'out': ...})."""
+    # -- LoRA adapters on the FFN projections (esme/lora.py): as in the attention block, the delta rides in an extension K-tile -----------
+    def _ffn_projections(self):
+        """(((name under the layer, module) of each up-projection -- SwiGLU: the gate, then fc), (name, module) of the down-projection)."""
+        if self.final_activation == 'gelu':
+            return (('final.1', self.final[1]),), ('final.3', self.final[3])
+        sw = self.final[1]
+        return (('final.1.activation', sw.activation), ('final.1.fc', sw.fc)), ('final.2', self.final[2])
+
+    def wrap_ffn_lora(self, up: bool, down: bool, wrap):
+        """ESM2.add_lora(layers=('ffn_up', 'ffn_down')): `wrap(projection)` (an esme.lora.LoRA around it) takes the place of the
+        up-projection (`final[1]`; SwiGLU: `final[1].activation` and `final[1].fc`, one wrapper each) and / or of the down-projection
+        (`final[3]`; SwiGLU: `final[2]`)."""
+        if up:
+            if self.final_activation == 'gelu':
+                self.final[1] = wrap(self.final[1])
+            else:
+                sw = self.final[1]
+                sw.activation, sw.fc = wrap(sw.activation), wrap(sw.fc)
+        if down:
+            i = 3 if self.final_activation == 'gelu' else 2
+            self.final[i] = wrap(self.final[i])
+        self._has_lora = bool(up or down)
+        self._derived.clear('lora')
+
+    def _ffn_lora_weights(self, lora_names, fold: bool):
+        """Derived weights of the FFN adapters `lora_names` selects (None / empty: all), cached like FlashMultiheadAttention._lora_weights on
+        the selection, the scalings, the parameters' version counters and the base form's key:
+        {'up': (X, A, c1A, bA, [W | s B | 0]) or None, 'down': (X, A, [W_d | s B | 0]) or None}.  SwiGLU: the gate's adapter rows come
+        first in A, then fc's, and the rows of s B follow the 32-row gate / fc interleave of SwiGLU._build_pack -- the gate adapter's
+        columns are zero in the fc rows and the other way round.  `fold`: for the LayerNorm-folded up-projection (A' = bf16(gamma A),
+        c1A, bA from `final[0]`).  On a quantised base that opted in the last element of either tuple is an ExtBlock (_ffn_lora_extended)."""
+        from esme.lora import LoRA
+        if self.padded:
+            raise NotImplementedError('LoRA adapters are not implemented for padded layouts (head dim 24 / a width that is not a multiple of 64)')
+        quantised = self._q4_up is not None or self._q4_down is not None
+        if quantised and not self._qlora:
+            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters, '
+                                      'unless they were attached with add_lora(quantized_base=True))')
+        ups, (_, down) = self._ffn_projections()
+        mods = [m for _, m in (*ups, ('', down)) if isinstance(m, LoRA)]
+        sel = tuple(m.select(lora_names) for m in mods)
+        params = [t for m, s in zip(mods, sel) for t in m.params(s)]
+        scalings = tuple(float(m.scaling) for m in mods)
+        ln = self.final[0]
+        if quantised:
+            key = (bool(fold), sel, scalings, 'quantised base', version_key(*params, *((ln.weight, ln.bias) if fold else ())))
+        else:
+            if fold:
+                self._pack_fold()
+            base_key = self._derived.key('fold') if fold else version_key(*(m.weight for _, m in ups))
+            key = (bool(fold), sel, scalings, base_key, version_key(down.weight, *params))
+        return self._derived.get('lora', key, self._build_ffn_lora, lora_names, fold, quantised)
+
+    def _build_ffn_lora(self, lora_names, fold: bool, quantised: bool):
+        from esme.lora import LoRA, ext_width
+        ups, (_, down) = self._ffn_projections()
+        ln, E, F = self.final[0], self.embed_dim, ups[0][1].out_features
+        dev = ln.weight.device
+        res = {'up': None, 'down': None}
+        blocks = [(i, *m.stacked(m.select(lora_names))) for i, (_, m) in enumerate(ups) if isinstance(m, LoRA)]
+        if blocks:
+            A = torch.cat([b[1] for b in blocks], dim=0).contiguous()
+            X = ext_width(A.shape[0])
+            c1A = bA = None
+            if fold:
+                Af = A.float()
+                A = (Af * ln.weight.data.float().unsqueeze(0)).to(torch.bfloat16).contiguous()
+                c1A = A.float().sum(dim=1).contiguous()
+                bA = (Af @ ln.bias.data.float()).contiguous() if ln.bias is not None else torch.zeros_like(c1A)
+            parts = [torch.zeros(F, X, dtype=torch.bfloat16, device=dev) for _ in ups]     # the extension columns per projection ...
+            o = 0
+            for i, a, b in blocks:
+                parts[i][:, o:o + a.shape[0]] = b.to(torch.bfloat16)
+                o += a.shape[0]
+            ext = parts[0] if len(parts) == 1 else torch.cat([p.view(F // 32, 1, 32, X) for p in parts], dim=1).reshape(2 * F, X)      # ... interleaved like the weight
+            if quantised:
+                we = ExtBlock(ext.contiguous())
+            else:
+                we = torch.cat(((self._pack_fold() if fold else self._weights_up(False))[0].data, ext), dim=1).contiguous()
+            res['up'] = (X, A, c1A, bA, we)
+        if isinstance(down, LoRA):
+            A, B = down.stacked(down.select(lora_names))
+            X = ext_width(A.shape[0])
+            ext = torch.zeros(E, X, dtype=torch.bfloat16, device=dev)
+            ext[:, :B.shape[1]] = B.to(torch.bfloat16)
+            res['down'] = (X, A.contiguous(), ExtBlock(ext) if quantised else torch.cat((down.weight.data, ext), dim=1).contiguous())
+        return res
+
+    def _ffn_lora_extended(self, which: str, entry, fold: bool = False):
+        """[W | s B | 0] of the _ffn_lora_weights entry `which` ('up' / 'down'): the cached tensor, or, on a quantised base, the per-call
+        expansion in the weight scratch with the cached extension block copied next to it (FlashMultiheadAttention._lora_extended)."""
+        we = entry[-1]
+        if not isinstance(we, ExtBlock):
+            return we
+        q4 = self._q4_up if which == 'up' else self._q4_down
+        w = (q4.folded(entry[0]) if fold else q4.plain(entry[0]))[0]
+        w[:, q4.cols:].copy_(we.block)
+        return w
+
+    def ffn_lora_ext_widths(self, lora_names):
+        """(X of the FFN up-projection, X of the down-projection) for this selection (0: that GEMM has no adapter)."""
+        if not self._has_lora:
+            return 0, 0
+        lw = self._ffn_lora_weights(lora_names, True)
+        return (lw['up'][0] if lw['up'] else 0, lw['down'][0] if lw['down'] else 0)
+
+    def _ffn_lora(self, x, alpha, stream, x_stats, stats_out, lw, epi, ctx):
+        """_ffn with adapters (`lw`: _ffn_lora_weights, precision 'fast').  Up: the operand is [x | u] (LayerNorm-folded: the stream buffer
+        ctx.lora_x with u from esme_hip_lora_down_ln on the FFN LayerNorm's statistics; else [LN(x) | u] in a buffer of its own) against
+        [W | s B | 0].  Down: the up GEMM writes its activation into the first F columns of a (T, F + X) buffer, esme_hip_lora_down
+        (K = F) fills the rest, and the residual GEMM runs over K = F + X.  Every lora_B zero: the extensions add exact zeros."""
+        up, down = lw['up'], lw['down']
+        ups, (_, dmod) = self._ffn_projections()
+        T, E, F = x.shape[0], self.embed_dim, ups[0][1].out_features
+        ln = self.final[0]
+        mid = torch.empty(T, F + down[0], dtype=torch.bfloat16, device=x.device) if down is not None else None
+        act = mid[:, :F] if mid is not None else None
+        if x_stats is not None:
+            if up is None or self._q4_up is None:
+                w, _, c1, c2 = self._weights_up(True)
+            else:                                               # (the base is expanded once, below, next to its extension)
+                c1, c2 = self._q4_up.c1, self._q4_up.c2
+            a_op = x
+            if up is not None:
+                X, A, c1A, bA = up[:4]
+                xe = ctx.lora_x if ctx is not None else None
+                if xe is None or xe.data_ptr() != x.data_ptr() or xe.stride(0) != x.stride(0) or xe.shape[1] < E + X:
+                    xe = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)       # (a caller outside the model's forward: x moves once)
+                    xe[:, :E].copy_(x)
+                _hip.lora_down(xe[:, :E], A, xe[:, E:E + X], ln=(x_stats, E, ln.eps, c1A, bA))
+                a_op, w = xe[:, :E + X], self._ffn_lora_extended('up', up, True)
+            act = _hip.gemm_fused(a_op, w, None, epi, out=act, ln=(x_stats, E, ln.eps, c1, c2, None))
+        else:
+            if up is None:
+                w, b, _, _ = self._weights_up(False)
+                a_op = ln(x)
+            else:
+                X, A = up[:2]
+                a_op = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)
+                ln(x, out=a_op[:, :E])
+                _hip.lora_down(a_op[:, :E], A, a_op[:, E:])
+                w = self._ffn_lora_extended('up', up)
+                b = self._q4_up.bias if self._q4_up is not None else (ups[0][1].bias if len(ups) == 1 else None)
+            act = _hip.gemm_fused(a_op, w, b, epi, out=act)
+        if down is None:
+            wd, bd = self._weights_down()
+        else:
+            _hip.lora_down(act, down[1], mid[:, F:])
+            act, wd = mid, self._ffn_lora_extended('down', down)
+            bd = self._q4_down.bias if self._q4_down is not None else dmod.bias
+        return _hip.gemm_fused(act, wd, bd, _hip.EPI_RESIDUAL, alpha=alpha, stats_out=stats_out, **stream)
+
+    def _ffn(self, x, alpha, stream, x_stats=None, stats_out=None, ovf=None, lora_names=None, ctx=None):
+        """FFN branch onto the residual stream `stream` (ForwardContext.residual(...), or {'resid': ..., 'out': ...}).  `lora_names`: on a
+        layer with FFN adapters (ESM2.add_lora(layers=('ffn_up', 'ffn_down'))), the adapters to apply (None / empty: all of them)."""
         epi = _hip.EPI_GELU if self.final_activation == 'gelu' else _hip.EPI_SWIGLU
         f16 = x.dtype == torch.float16                       # precision 'half': the operand type travels with the tensors
+        if self._has_lora:
+            if self.training:
+                raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
+            if f16 or 'resid' not in stream:
+                raise NotImplementedError("LoRA adapters run in precision 'fast' only ('high', 'half' and 'exact' have no adapter path)")
+            lw = self._ffn_lora_weights(lora_names, x_stats is not None)
+            if lw['up'] is not None or lw['down'] is not None:
+                return self._ffn_lora(x, alpha, stream, x_stats, stats_out, lw, epi, ctx)
         if x_stats is not None:
             wf, _, c1, c2 = self._weights_up(True, f16, stream.get('pair_ext'))
             u = _hip.gemm_fused(x, wf, None, epi, ln=(x_stats, self.embed_dim, self.final[0].eps, c1, c2, ovf))
@@ -936,6 +1098,11 @@ class FlashTransformerLayer(nn.Module):
         quantised = any(q is not None for q in (self._q4_up, self._q4_down))
         ag.refuse(quantised and not self._qlora, f'quantised weights have no backward (load the model without quantization=; {ag.QLORA_HINT})')
         ag.check_frozen_norms((('final.0', self.final[0]),), self._qlora and quantised)
+        from esme.lora import LoRA
+        ups, down = self._ffn_projections()
+        for name, m in (*ups, down):
+            ag.refuse(isinstance(m, LoRA) and m.dropout_p > 0, f'LoRA dropout_p = {getattr(m, "dropout_p", 0)} > 0 is not implemented (dropout is out of scope)')
+            ag.check_linear(m.layer if isinstance(m, LoRA) else m, 'the FFN', self._qlora)
         self.self_attn.check_trainable()
 
     def forward_trainable(self, x, cu_lens, max_len, lora_names=None, pos=None):
@@ -945,16 +1112,12 @@ class FlashTransformerLayer(nn.Module):
         self.check_trainable()
         x = x + self.self_attn.forward_trainable(x, cu_lens, max_len, lora_names, pos) / self.residue_scaling
         h = ag.layer_norm(x, self.final[0])
+        ups, (_, down) = self._ffn_projections()               # (check_trainable went over them; each with the adapters `lora_names` selects)
         if self.final_activation == 'gelu':
-            for lin in (self.final[1], self.final[3]):
-                ag.check_linear(lin, 'the FFN', self._qlora)
-            y = ag.frozen_linear(torch.nn.functional.gelu(ag.frozen_linear(h, self.final[1], True)), self.final[3], True)
+            u = torch.nn.functional.gelu(ag.lora_linear(h, ups[0][1], lora_names))
         else:
-            sw = self.final[1]
-            for lin in (sw.activation, sw.fc, self.final[2]):
-                ag.check_linear(lin, 'the FFN', self._qlora)
-            y = ag.frozen_linear(torch.nn.functional.silu(ag.frozen_linear(h, sw.activation, True)) * ag.frozen_linear(h, sw.fc, True), self.final[2], True)
-        return x + y / self.residue_scaling
+            u = torch.nn.functional.silu(ag.lora_linear(h, ups[0][1], lora_names)) * ag.lora_linear(h, ups[1][1], lora_names)
+        return x + ag.lora_linear(u, down, lora_names) / self.residue_scaling
 
     def forward(self, x, cu_lens, max_len, lora_names=None, ctx: Optional[ForwardContext] = None,
                 inplace: bool = False):
@@ -973,10 +1136,10 @@ class FlashTransformerLayer(nn.Module):
             i = self.self_attn.layer_index
             site = ctx.residual(i, 0, x, y)
             self.self_attn(x, cu_lens, max_len, lora_names, ctx, alpha=alpha, x_stats=ctx.sums, stats_out=ctx.part_b, stream=site)
-            self._ffn(y, alpha, site if inplace else ctx.residual(i, 1, y, y), x_stats=ctx.part_b, stats_out=ctx.part_a)
+            self._ffn(y, alpha, site if inplace else ctx.residual(i, 1, y, y), x_stats=ctx.part_b, stats_out=ctx.part_a, lora_names=lora_names, ctx=ctx)
             ctx.sums = ctx.part_a                               # row sums of the layer output
             return y
         if self.padded:
             raise NotImplementedError('padded layouts need a folding context (ForwardContext(fold=True))')
         self.self_attn(x, cu_lens, max_len, lora_names, ctx, resid=x, alpha=alpha, out=y)
-        return self._ffn(y, alpha, {'resid': y, 'out': y})
+        return self._ffn(y, alpha, {'resid': y, 'out': y}, lora_names=lora_names, ctx=ctx)

@@ -623,6 +623,7 @@ class ESM2(nn.Module):
 
     # -- LoRA adapters (inference; esme/lora.py) ---------------------------------------------------------------------
     _LORA_TARGETS = (('query', 'q'), ('key', 'k'), ('value', 'v'), ('output', 'out'))
+    _LORA_FFN_TARGETS = ('ffn_up', 'ffn_down')       # the layer's FFN projections (FlashTransformerLayer.wrap_ffn_lora)
 
     @property
     def has_lora(self) -> bool:
@@ -653,10 +654,11 @@ class ESM2(nn.Module):
         return list(mods[0].lora_A.keys()) if mods else []
 
     def _lora_stream(self, x, lora, ctx):
-        """The residual stream moved into the first E columns of a (T, E + X) buffer (X: the extension K-tile of the QKV GEMM for this
-        adapter selection): every layer's esme_hip_lora_down writes next to the stream, and the LayerNorm-folded QKV GEMM reads [x | u]
-        as ONE operand.  Returns the stream as a view of that buffer (x itself when q, k and v carry no adapter)."""
-        X = self.layers[0].self_attn.lora_ext_widths(lora)[0]
+        """The residual stream moved into the first E columns of a (T, E + X) buffer (X: the wider of the extension K-tiles of the QKV GEMM
+        and of the FFN up-projection for this adapter selection): every layer's esme_hip_lora_down writes next to the stream, and the
+        LayerNorm-folded QKV / FFN-up GEMM reads [x | u] as ONE operand.  Returns the stream as a view of that buffer (x itself when
+        neither GEMM carries an adapter)."""
+        X = max(self.layers[0].self_attn.lora_ext_widths(lora)[0], self.layers[0].ffn_lora_ext_widths(lora)[0])
         if not X or not ctx.fold or x.shape[1] % 64:
             return x
         T, E = x.shape
@@ -666,7 +668,10 @@ class ESM2(nn.Module):
 
     def add_lora(self, rank=16, alpha=16, layers=('query', 'value', 'output'), dropout_p=0., adapter_names=None, quantized_base=False):
         """Attach LoRA adapters (reference esm.py:495-543): every layer's `self_attn.{q,k,v,out}` named in `layers` becomes an
-        esme.lora.LoRA around the projection, with one (A, B) pair per name in `adapter_names` (default ['default']); A is initialised
+        esme.lora.LoRA around the projection, with one (A, B) pair per name in `adapter_names` (default ['default']).  Beyond the
+        reference's four names, 'ffn_up' wraps the FFN up-projection (`final[1]` of a GELU layer; SwiGLU's `final[1].activation` and
+        `final[1].fc`, one adapter of that rank each) and 'ffn_down' the down-projection (`final[3]` / `final[2]`): with all six,
+        every linear layer of the block carries an adapter (the QLoRA recipe).  A is initialised
         like the reference's (Kaiming uniform), B with zeros, so fresh adapters leave the model's output unchanged.  Inference only:
         `dropout_p` is stored (and written by save_lora) but never applied.  Refuses what cannot run the adapters: a precision other
         than 'fast', quantised base weights, padded layouts (ESM2-35M), ranks outside 1 .. 64.
@@ -677,7 +682,8 @@ class ESM2(nn.Module):
         trainable and the LayerNorms stay frozen (mark_trainable / a LayerNorm that requires grad keep raising)."""
         from esme.lora import LoRA
         wanted = set(layers)
-        assert len(wanted.difference({'query', 'value', 'key', 'output'})) == 0, 'layers must be a subset of {"query", "value", "key", "output"}'
+        assert len(wanted.difference({'query', 'value', 'key', 'output', *self._LORA_FFN_TARGETS})) == 0, \
+            'layers must be a subset of {"query", "value", "key", "output", "ffn_up", "ffn_down"}'
         if self.has_lora:
             raise NotImplementedError('LoRA adapters are already attached to this model (a second set would wrap the first)')
         if self.precision != 'fast':
@@ -691,12 +697,15 @@ class ESM2(nn.Module):
         if not (1 <= int(rank) <= 64) or int(rank) != rank:
             raise NotImplementedError(f'LoRA rank {rank}: integer ranks 1 .. 64 are served')
         self.lora_kwargs = {'rank': rank, 'alpha': alpha, 'dropout_p': dropout_p,
-                            'layers': [long for long, _ in self._LORA_TARGETS if long in wanted], 'names': adapter_names}
+                            'layers': [long for long in (*(l for l, _ in self._LORA_TARGETS), *self._LORA_FFN_TARGETS) if long in wanted],
+                            'names': adapter_names}
         for layer in self.layers:
             att = layer.self_attn
             for long, short in self._LORA_TARGETS:
                 if long in wanted:
                     setattr(att, short, LoRA(getattr(att, short), rank=rank, alpha=alpha, dropout_p=dropout_p, names=adapter_names))
+            layer.wrap_ffn_lora('ffn_up' in wanted, 'ffn_down' in wanted,
+                                lambda lin: LoRA(lin, rank=rank, alpha=alpha, dropout_p=dropout_p, names=adapter_names))
             att._has_lora = True
             att._qlora = layer._qlora = bool(quantised)      # (quantised here means: and opted in)
         self.__dict__['_lora_attached'] = True

@@ -9,7 +9,10 @@ the adapters could no longer be selected per call).  The delta rides in an EXTEN
     [x | u] [W | s B]^T = x W^T + u (s B)^T,        u = x A^T   (esme_hip_lora_down, written next to x in the same buffer)
 
 so it accumulates in fp32 inside the MFMA chain and every fused epilogue of the hot path (LayerNorm fold, rotary, q pre-scale,
-residual, row statistics) is untouched (esme/attention.py).  That fused forward is for inference: it has no
+residual, row statistics, GELU, SwiGLU) is untouched (esme/attention.py).  The wrapped projections are the
+reference's four (q, k, v, out of the attention block) and, beyond it, the FFN's (`ESM2.add_lora(layers=(..., 'ffn_up', 'ffn_down'))`:
+the up-projection -- SwiGLU: its gate and fc, one wrapper each -- and the down-projection, whose adapter reads K = the FFN width).
+That fused forward is for inference: it has no
 backward, dropout is stored and ignored in eval(), a forward in train() raises.  Adapters are trained through
 `model.forward_trainable` (esme/autograd.py), the reference's unfused data flow with a grad_fn.
 """

@@ -541,7 +541,11 @@ int esme_hip_relu_linear(const void* h, int64_t ldh, const void* w, int64_t ldw,
  *  as zeros, nothing outside the X columns is touched (u may be the columns E .. E+X-1 of the buffer that holds x);  c1, bA: fp32 (rank).
  * Limits: E % 64 == 0, X % 64 == 0 (else ESME_ERR_UNSUPPORTED), X <= 256 in this build (else ESME_ERR_UNSUPPORTED), 0 < rank <= X,
  * ldx >= E, ldu >= X, both multiples of 8, 16-byte aligned x, A, u (else ESME_ERR_ARG).  T = 0 is a no-op.  fp32 accumulation
- * (v_mfma_f32_16x16x32_bf16), one rounding. */
+ * (v_mfma_f32_16x16x32_bf16), one rounding.
+ * K range: E is the K of the projection the adapters belong to -- the model width (320 .. 2 560) for q / k / v / out and the FFN
+ * up-projection, the FFN width F (512 .. 10 240) for the FFN down-projection, where x is the activation in the first F columns of the
+ * (T, F + X) operand (ldx = F + X).  Any multiple of 64 is served: row offsets (t * ldx, j * E) are formed in 64 bits, and the
+ * in-row offsets k < E stay far inside 32 bits. */
 int esme_hip_lora_down(const void* x, int64_t ldx, const void* A, int rank, int64_t T, int E, int X, void* u, int64_t ldu,
                        void* stream);
 int esme_hip_lora_down_ln(const void* x, int64_t ldx, const void* A, int rank, int64_t T, int E, int X, void* u, int64_t ldu,
