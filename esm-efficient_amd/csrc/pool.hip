@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void relu_linear_kernel(const void* __restrict
             float f[8];
             load8<F32>(h, r * ldh + k, f);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) f[i] = fmaxf(f[i], 0.f);
+            for (int i = 0; i < 8; ++i) f[i] = f[i] < 0.f ? 0.f : f[i];          // not fmaxf: v_max returns its non-NaN operand, relu(NaN) is NaN
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) {
                 if (j0 + jj < N) {

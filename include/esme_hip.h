@@ -524,7 +524,8 @@ int esme_hip_attn_pool(const void* x, int64_t ldx, const int32_t* cu_lens, int B
 /* y[r, j] = b[j] + sum_k W[j, k] relu(h[r, k]), j < N <= 64 (else ESME_ERR_UNSUPPORTED): the last Linear of the pooling heads after
  * their ReLU (esme/pooling.py:210-211 final(relu(linear(x))), esme/head.py:59-63).  h: (M, K) bf16 (dtype_f32 = 0) or fp32 (1), row
  * stride ldh; W: bf16 (N, K) row stride ldw (a multiple of 8); bias: bf16 (N) or NULL; y: (M, N) in h's dtype, row stride ldy.
- * K % 8 == 0, 16-byte aligned h and W rows.  fp32 accumulation, one rounding. */
+ * K % 8 == 0, 16-byte aligned h and W rows.  fp32 accumulation, one rounding.  relu(NaN) is NaN, as torch's: a row of h that holds a
+ * NaN gives a NaN row of y, never the bias. */
 int esme_hip_relu_linear(const void* h, int64_t ldh, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
                          int64_t M, int N, int K, int dtype_f32, void* stream);
 

@@ -27,9 +27,9 @@ def add(id, symbols, build):
     CASES.append(G.Spec(id, tuple('esme_hip_' + s for s in symbols.split()), build))
 
 
-def bwd_case(lengths, dt, with_dx):
+def bwd_case(lengths, dt, with_dx, C=3):
     from esme import _hip_attn_pool_bwd as HB
-    E, H, C = 64, 4, 3
+    E, H = 64, 4
     J = C * H
     c = PB.make_operands(lengths, E, H, C, dt, seed=17)
     T, B = sum(lengths), len(lengths)

@@ -516,8 +516,7 @@ for _T, _E in [(1, 64), (37, 1280), (259, 320)]:
         add(f'{_kind}-T{_T}-E{_E}', _sym, lambda k=_kind, T=_T, E=_E: stream_case(k, T, E))
 
 
-def softmax_case(dt, V, log):
-    T = 37
+def softmax_case(dt, V, log, T=37):
     ops = [Operand('x', rnd((T, V), 1, 3.0, dt)), out('y', (T, V), dt)]
 
     def call(v):
