@@ -23,6 +23,11 @@
    tokens and the key weight.  `SegmentMean`: forward = esme_hip_segment_mean, backward =
    esme_hip_segment_mean_bwd (include/esme_hip_segment_mean_bwd.h): no host read of cu_lens, so the node does not stall the stream.
 
+ - `LinearCrossEntropy`: a linear layer of at most 64 outputs fused with the cross-entropy of its logits over packed rows (the loss of a
+   per-residue head and of the masked-LM head's vocabulary projection): forward = esme_hip_linear_xent_fwd, backward =
+   esme_hip_linear_xent_bwd (include/esme_hip_linear_xent.h).  The logits are never materialised, the labelled rows are selected
+   inside the kernel (no nonzero), the upstream gradient stays on the device: neither direction synchronises with the host.
+
 `forward_trainable` of the attention block, the layer and the model (esme/attention.py, esme/esm.py) is written with the first two and
 torch ops, in the reference's unfused data flow; `forward_trainable` of the task heads (esme/pooling.py, esme/head.py) with the pooling
 nodes and torch ops.
@@ -34,7 +39,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-from esme import _hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_embed_positions_bwd, _hip_gemm_wgrad, _hip_segment_mean_bwd
+from esme import (_hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_embed_positions_bwd, _hip_gemm_wgrad, _hip_linear_xent,
+                  _hip_segment_mean_bwd)
 from esme.nn import weight_t
 
 
@@ -239,6 +245,41 @@ class SegmentMean(torch.autograd.Function):
         if dy.stride(1) != 1 or (dy.stride(0) * dy.element_size()) % 16 or dy.data_ptr() % 16:
             dy = dy.contiguous()
         return _hip_segment_mean_bwd.segment_mean_bwd(dy, cu_lens, ctx.rows), None
+
+
+class LinearCrossEntropy(torch.autograd.Function):
+    """The float32 device scalar  sum_t l_t  (`mean` False) or  sum_t l_t / sum_kept cw[y_t]  (`mean` True; 0 when no weight is kept,
+    where torch returns NaN) with l_t = cw[y_t] (logsumexp(x_t w^T + b) - (x_t w^T + b)[y_t]) on the rows whose label is neither
+    `ignore_index` nor outside [0, C), and 0 on the others.  x (T, E), w (C, E), b (C) or None in bfloat16, labels (T,) int32 / int64,
+    class_weight (C,) float32 or None.  Differentiable in x, w and b; dw and db are rounded to bfloat16 once."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, labels, ignore_index, class_weight, mean):
+        x, w = _kernel_rows(x.detach()), _kernel_rows(w.detach())
+        b = None if b is None else b.detach().contiguous()
+        labels = labels.contiguous()
+        if labels.data_ptr() % 16:
+            labels = labels.clone()
+        sums, _, lse = _hip_linear_xent.linear_xent_fwd(x, w, b, labels, ignore_index, class_weight, mean)
+        ctx.save_for_backward(x, w, b, labels, class_weight, lse, sums)
+        ctx.args = (int(ignore_index), bool(mean))
+        return sums[2].clone()                                    # (its own storage: an in-place op on the loss leaves `sums` alone)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, b, labels, class_weight, lse, sums = ctx.saved_tensors
+        ignore_index, mean = ctx.args
+        g = g.to(torch.float32).reshape(1)
+        if g.data_ptr() % 16:
+            g = g.clone()
+        want_dx = ctx.needs_input_grad[0]
+        want_dw = ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2])
+        dx = dw = db = None
+        if want_dx or want_dw:
+            dx, dw, db = _hip_linear_xent.linear_xent_bwd(x, w, b, labels, lse, sums, g, ignore_index, class_weight, mean,
+                                                          want_dx=want_dx, want_dw=want_dw)
+        return (dx, dw if ctx.needs_input_grad[1] else None, db if (b is not None and ctx.needs_input_grad[2]) else None,
+                None, None, None, None)
 
 
 def relu_mlp(x: torch.Tensor, lin, final) -> torch.Tensor:

@@ -6,7 +6,8 @@ greedy packing rule follow `esme/data.py:12-60,63-162` of the reference.  `Maske
 `MaskedFastaTokenDataset` add the masked-token corruption of `esme.alphabet.mask_tokens` for
 masked-LM training (the reference's constructor arguments and item layouts, data.py:165-245);
 `LabeledDataset` pairs in-memory sequences with one label each for supervised fine-tuning (esme.trainer.RegressionModel; the
-reference's constructor arguments and item dict, data.py:377-407); the Lightning data modules (data.py:247-374, 410-520:
+reference's constructor arguments and item dict, data.py:377-407) and `ResidueLabeledDataset` with one label per residue
+(esme.trainer.ResidueModel); the Lightning data modules (data.py:247-374, 410-520:
 MaskedFastaDataModule, LabeledDataModule) stay out of scope.
 """
 from __future__ import annotations
@@ -175,6 +176,61 @@ class LabeledDataset(Dataset):
         batch = self.sampler[idx]
         token, indices, cu_lens, max_len = tokenize_unpad([self.truncate(self.seqs[i]) for i in batch])
         label = torch.tensor([float(self.labels[i]) for i in batch], dtype=torch.float32)
+        return {'token': token, 'cu_lens': cu_lens, 'max_len': max_len, 'indices': indices, 'label': label}
+
+    def to_dataloader(self, num_workers=0, **kwargs):
+        """One packed batch per item (batch_size=None); see FastaTokenDataset.to_dataloader on `num_workers`."""
+        return DataLoader(self, num_workers=num_workers, batch_size=None, **kwargs)
+
+
+class ResidueLabeledDataset(Dataset):
+    """Item i = the i-th token-budget batch of in-memory sequences with one label per residue, as LabeledDataset's dict (`token`,
+    `cu_lens`, `max_len`, `indices`: the same sampler, hence the same batches for the same seed) with `label` an int64 tensor (T,)
+    aligned with the packed `token`: `ignore_index` on the `<cls>` / `<eos>` rows and wherever the user's label is negative, the
+    user's integer elsewhere -- what esme.head.ResidueHead.loss takes.
+
+    labels[i]: a sequence of len(seqs[i]) integers, or with `classes` (e.g. 'HEC') a string of that length whose characters map to
+    their position in `classes`; any other character maps to `ignore_index`.  A label sequence whose length differs from its
+    protein's is a ValueError here, at construction.  `truncate_len` cuts sequence and labels alike (the budget is taken over the full
+    lengths, as in LabeledDataset)."""
+
+    def __init__(self, seqs, labels, token_per_batch, shuffle=True, random_state=None, truncate_len=None, classes=None, ignore_index=-100):
+        if len(seqs) != len(labels):
+            raise ValueError(f'ResidueLabeledDataset: {len(seqs)} sequences but {len(labels)} label sequences')
+        for i, (s, l) in enumerate(zip(seqs, labels)):
+            if len(s) != len(l):
+                raise ValueError(f'ResidueLabeledDataset: sequence {i} has {len(s)} residues but {len(l)} labels')
+            if classes is not None and not isinstance(l, str):
+                raise ValueError(f'ResidueLabeledDataset: classes={classes!r} maps label strings, but labels[{i}] is {type(l).__name__}')
+        self.seqs, self.labels, self.truncate_len = seqs, labels, truncate_len
+        self.classes, self.ignore_index = classes, int(ignore_index)
+        self._class_of = None if classes is None else {ch: k for k, ch in enumerate(classes)}
+        self.sampler = list(TokenSizeBatchSampler([len(s) for s in seqs], token_per_batch, shuffle=shuffle, random_state=random_state))
+
+    def truncate(self, seq):
+        return seq if self.truncate_len is None else seq[:self.truncate_len]
+
+    def encode_labels(self, lab) -> torch.Tensor:
+        """int64 (len(lab) + 2,): `ignore_index`, the (truncated) labels, `ignore_index`."""
+        lab = self.truncate(lab)
+        if self._class_of is not None:
+            body = torch.tensor([self._class_of.get(ch, self.ignore_index) for ch in lab], dtype=torch.int64)
+        else:
+            body = torch.as_tensor([int(v) for v in lab], dtype=torch.int64).reshape(-1)
+            body = torch.where(body < 0, torch.full_like(body, self.ignore_index), body)
+        edge = torch.full((1,), self.ignore_index, dtype=torch.int64)
+        return torch.cat((edge, body, edge))
+
+    def __len__(self):
+        return len(self.sampler)
+
+    def __getitem__(self, idx):
+        batch = self.sampler[idx]
+        token, indices, cu_lens, max_len = tokenize_unpad([self.truncate(self.seqs[i]) for i in batch])
+        label = torch.cat([self.encode_labels(self.labels[i]) for i in batch])
+        if label.numel() != token.numel():
+            raise ValueError(f'ResidueLabeledDataset: batch {idx} tokenises to {token.numel()} rows but carries {label.numel()} labels '
+                             '(a sequence holds a multi-character token?)')
         return {'token': token, 'cu_lens': cu_lens, 'max_len': max_len, 'indices': indices, 'label': label}
 
     def to_dataloader(self, num_workers=0, **kwargs):

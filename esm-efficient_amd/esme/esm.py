@@ -878,6 +878,27 @@ class ESM2(nn.Module):
                 return torch.cat((x, *taps), dim=-1)
             return self.lm_head.forward_trainable(x) if logits else x
 
+    def masked_lm_loss(self, masked_tokens, pad_args, tokens, mask, lora_names=None, checkpoint_layers=False, reduction='mean'):
+        """The masked-LM loss of a training step as a float32 device scalar with a grad_fn, without a host synchronisation: the
+        sync-free form of `esme.cross_entropy(model.forward_trainable(masked_tokens, pad_args, ...), tokens, mask)`.
+        forward_trainable(..., logits=False), then the LM head's dense -> GELU -> LayerNorm (RobertaLMHead.features_trainable, the ops
+        of its forward_trainable), then the vocabulary projection fused with the cross-entropy (esme.autograd.LinearCrossEntropy on
+        `lm_head.final`): the (T, V) logits are never formed, and the rows are selected by labels built on the device -- `tokens` where
+        `mask` holds and the token is not `<pad>`, an ignored label elsewhere -- instead of a boolean index (a nonzero).  masked_tokens
+        / tokens / mask: packed (T,) with pad_args = (cu_lens, max_len), or 2-D (B, S) with pad_args None.  The two routes agree to
+        rounding but are not bit-equal: esme.cross_entropy reads logits that were rounded to bfloat16 first.  reduction: 'mean' (0,
+        not NaN, when no row is selected) or 'sum'."""
+        from esme.loss import linear_cross_entropy
+        if tokens.shape != masked_tokens.shape or mask.shape != masked_tokens.shape:
+            raise ValueError(f'masked_lm_loss: masked_tokens {tuple(masked_tokens.shape)}, tokens {tuple(tokens.shape)} and mask '
+                             f'{tuple(mask.shape)} must have one shape')
+        x = self.forward_trainable(masked_tokens, pad_args, lora_names=lora_names, logits=False, checkpoint_layers=checkpoint_layers)
+        with _hip.stream_scope(self.embed_tokens.weight.device):
+            h = self.lm_head.features_trainable(x)
+            ignore = -100
+            labels = torch.where(mask.to(torch.bool) & (tokens != self.alphabet.padding_idx), tokens, torch.full_like(tokens, ignore))
+            return linear_cross_entropy(h, self.lm_head.final, labels.reshape(-1), ignore_index=ignore, reduction=reduction)
+
     def mark_lmhead(self, trainable=True):
         for p in self.lm_head.parameters():
             p.requires_grad_(trainable)

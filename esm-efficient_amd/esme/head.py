@@ -52,11 +52,17 @@ class RobertaLMHead(nn.Module):
         """dense -> GELU -> LayerNorm -> vocabulary projection on (..., E) features in torch ops on the head's own parameters (frozen
         projections of GEMM-tile shape run on the kernel: esme.autograd.frozen_linear), so that mark_lmhead(True) trains it."""
         from esme import autograd as ag
-        ag.refuse(self.phys_dim != self.embed_dim, 'the padded layout has no backward')
         shape = x.shape
-        h = torch.nn.functional.gelu(ag.frozen_linear(x.reshape(-1, shape[-1]), self.dense))
-        y = ag.frozen_linear(ag.layer_norm(h, self.layer_norm), self.final)
+        y = ag.frozen_linear(self.features_trainable(x), self.final)
         return y.view(*shape[:-1], y.shape[-1])
+
+    def features_trainable(self, x):
+        """The part of `forward_trainable` before the vocabulary projection: dense -> GELU -> LayerNorm on (..., E) features, as
+        (rows, E).  What model.masked_lm_loss hands to the fused projection + cross-entropy instead of materialising the logits."""
+        from esme import autograd as ag
+        ag.refuse(self.phys_dim != self.embed_dim, 'the padded layout has no backward')
+        h = torch.nn.functional.gelu(ag.frozen_linear(x.reshape(-1, x.shape[-1]), self.dense))
+        return ag.layer_norm(h, self.layer_norm)
 
     def forward(self, features):
         shape = features.shape
@@ -110,3 +116,37 @@ class ClsHead(nn.Module):
         ag.check_head_input(x, [(n, p) for n, p in self.named_parameters()], 'ClsHead')
         pooled = ag.SegmentMean.apply(x, cu_lens)
         return ag.relu_mlp(pooled, self.head[0], self.head[2]).squeeze(-1)
+
+
+class ResidueHead(nn.Module):
+    """A label per residue: one Linear `classifier` over the rows of the representation, the layer Hugging Face's
+    EsmForTokenClassification calls by the same name (state-dict keys `classifier.weight`, `classifier.bias`: a head trained there
+    loads here).  `forward(x)` -> (..., num_labels) bfloat16 logits on the GEMM kernel and `predict(x)` -> the argmax labels, both
+    inference only; `loss(x, labels)` is the training route: esme.loss.linear_cross_entropy on `classifier`, which never forms the
+    logits.  At most 64 labels.  Parameters are bfloat16 whatever `dtype` says (fp32 checkpoints cast on load_state_dict) and are
+    created with requires_grad=False; opt in with `head.requires_grad_(True)`."""
+
+    def __init__(self, embed_dim, num_labels, dtype=torch.bfloat16):
+        super().__init__()
+        if embed_dim % 8 != 0:
+            raise ValueError('ResidueHead: embed_dim must be a multiple of 8')
+        if not 1 <= num_labels <= 64:
+            raise ValueError(f'ResidueHead: num_labels must be in 1 .. 64 (the fused loss serves one MFMA column tile), got {num_labels}')
+        self.embed_dim, self.num_labels = embed_dim, num_labels
+        self.classifier = Linear(embed_dim, num_labels, dtype=torch.bfloat16)
+
+    def forward(self, x):
+        if x.dtype != torch.bfloat16:
+            raise TypeError(f'ResidueHead: x must be bfloat16, got {x.dtype}')
+        with torch.no_grad():
+            return self.classifier(x.detach())
+
+    def predict(self, x):
+        """(...) int64: the label of the largest logit of every row."""
+        return self.forward(x).argmax(dim=-1)
+
+    def loss(self, x, labels, ignore_index=-100, weight=None, reduction='mean'):
+        """Cross entropy of classifier(x) against `labels` (...) as a float32 device scalar with a grad_fn: see
+        esme.loss.linear_cross_entropy (rows labelled `ignore_index` or outside [0, num_labels) are ignored; no host synchronisation)."""
+        from esme.loss import linear_cross_entropy
+        return linear_cross_entropy(x, self.classifier, labels, ignore_index=ignore_index, weight=weight, reduction=reduction)
