@@ -10,6 +10,7 @@ from esme.loss import cross_entropy, nll_loss               # noqa: F401
 from esme.contacts import ContactFeatureAccumulator, ContactHead, fit_contact_head      # noqa: F401
 from esme.attention_maps import AttentionMapAccumulator      # noqa: F401
 from esme import optim                                      # noqa: F401  (esme.optim.AdamW: fp32 master weights, one fused HIP step)
+from esme import crf                                        # noqa: F401  (esme.crf.CRF: a linear-chain CRF over packed per-residue scores)
 from esme import trainer                                    # noqa: F401  (esme.trainer.RegressionModel: supervised fine-tuning)
 
 __all__ = ['ESM', 'ESM2', 'ESM1b', 'ESM1v', 'ESMC', 'ContactHead', 'ContactFeatureAccumulator', 'fit_contact_head', 'tokenize', 'tokenize_unpad', 'cross_entropy', 'nll_loss']

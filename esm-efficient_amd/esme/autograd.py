@@ -28,6 +28,9 @@
    esme_hip_linear_xent_bwd (include/esme_hip_linear_xent.h).  The logits are never materialised, the labelled rows are selected
    inside the kernel (no nonzero), the upstream gradient stays on the device: neither direction synchronises with the host.
 
+ - `CRFLogPartition`: log Z of a linear-chain CRF per packed sequence (include/esme_hip_crf.h): forward = esme_hip_crf_fwd (the forward
+   algorithm), backward = one call of esme_hip_crf_bwd (the backward algorithm) with the (B,) upstream gradient left on the device.
+
 `forward_trainable` of the attention block, the layer and the model (esme/attention.py, esme/esm.py) is written with the first two and
 torch ops, in the reference's unfused data flow; `forward_trainable` of the task heads (esme/pooling.py, esme/head.py) with the pooling
 nodes and torch ops.
@@ -39,8 +42,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-from esme import (_hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_embed_bwd, _hip_embed_positions_bwd, _hip_gemm_wgrad, _hip_linear_xent,
-                  _hip_segment_mean_bwd)
+from esme import (_hip, _hip_attn_bwd, _hip_attn_pool_bwd, _hip_crf, _hip_embed_bwd, _hip_embed_positions_bwd, _hip_gemm_wgrad,
+                  _hip_linear_xent, _hip_segment_mean_bwd)
 from esme.nn import weight_t
 
 
@@ -280,6 +283,45 @@ class LinearCrossEntropy(torch.autograd.Function):
                                                           want_dx=want_dx, want_dw=want_dw)
         return (dx, dw if ctx.needs_input_grad[1] else None, db if (b is not None and ctx.needs_input_grad[2]) else None,
                 None, None, None, None)
+
+
+def _f32_rows(t: torch.Tensor) -> torch.Tensor:
+    """t (T, C) as the CRF kernels read it: float32, unit column stride, a 16-byte aligned base."""
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(1) != 1 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class CRFLogPartition(torch.autograd.Function):
+    """logz (B,) float32: per sequence of `cu_lens` the log of the summed exponentiated scores of every label path that `tags` allows
+    (int32 (T,): a label in [0, C) constrains its row, esme._hip_crf.FREE leaves it free, anything else takes the row out of the
+    chain; an empty chain gives 0).  emissions (T, C); transitions (C, C) with [i][j] the score of moving from i to j, start, end (C,).
+    Differentiable in the first four, all in float32; neither direction synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, emissions, transitions, start, end, tags, cu_lens):
+        ctx.e_dtype = emissions.dtype
+        e = _f32_rows(emissions)
+        A, s, n = (t.detach().float().contiguous() for t in (transitions, start, end))
+        tags = tags.to(torch.int32).contiguous()
+        cu_lens = cu_lens.to(torch.int32).contiguous()
+        logz, alpha = _hip_crf.crf_fwd(e, A, s, n, cu_lens, tags)
+        ctx.save_for_backward(e, A, s, n, tags, cu_lens, alpha, logz)
+        return logz.clone()                                       # (its own storage: an in-place op on the result leaves the saved logz alone)
+
+    @staticmethod
+    def backward(ctx, g):
+        e, A, s, n, tags, cu_lens, alpha, logz = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        want = any(ctx.needs_input_grad[1:4])
+        d_e, d_t, d_s, d_n = _hip_crf.crf_bwd(e, A, s, n, cu_lens, tags, alpha, logz, g, want_params=want)
+        pick = lambda i, t: t if (t is not None and ctx.needs_input_grad[i]) else None
+        return (pick(0, d_e.to(ctx.e_dtype)), pick(1, d_t), pick(2, d_s), pick(3, d_n), None, None)
 
 
 def relu_mlp(x: torch.Tensor, lin, final) -> torch.Tensor:

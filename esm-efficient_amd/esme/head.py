@@ -150,3 +150,44 @@ class ResidueHead(nn.Module):
         esme.loss.linear_cross_entropy (rows labelled `ignore_index` or outside [0, num_labels) are ignored; no host synchronisation)."""
         from esme.loss import linear_cross_entropy
         return linear_cross_entropy(x, self.classifier, labels, ignore_index=ignore_index, weight=weight, reduction=reduction)
+
+
+class ResidueCRFHead(nn.Module):
+    """A label per residue with a linear-chain CRF on top: `classifier`, the Linear of ResidueHead (the same state-dict keys), gives
+    the emissions and `crf` (esme.crf.CRF; keys `crf.transitions`, `crf.start_transitions`, `crf.end_transitions`) scores whole label
+    paths -- the output layer of signal-peptide and topology predictors, where independent per-residue softmaxes produce label
+    sequences that cannot occur.  `loss(x, labels, cu_lens)` is the training route, `predict(x, cu_lens)` the Viterbi path,
+    `marginals(x, cu_lens)` the posterior label probabilities; all take packed rows.  `classifier` is bfloat16, the CRF's parameters
+    float32; both are created with requires_grad=False; opt in with `head.requires_grad_(True)`.  **crf_kwargs: CRF's allowed= masks."""
+
+    def __init__(self, embed_dim, num_labels, **crf_kwargs):
+        super().__init__()
+        from esme.crf import CRF
+        if embed_dim % 8 != 0:
+            raise ValueError('ResidueCRFHead: embed_dim must be a multiple of 8')
+        self.embed_dim, self.num_labels = embed_dim, num_labels
+        self.crf = CRF(num_labels, **crf_kwargs)
+        self.classifier = Linear(embed_dim, num_labels, dtype=torch.bfloat16)
+
+    def emissions_trainable(self, x):
+        """classifier(x) as float32 (T, num_labels) in torch ops on the head's own parameters, with a grad_fn."""
+        if x.dtype != torch.bfloat16:
+            raise TypeError(f'ResidueCRFHead: x must be bfloat16, got {x.dtype}')
+        x = x.reshape(-1, x.shape[-1])
+        return torch.nn.functional.linear(x, self.classifier.weight, self.classifier.bias).float()
+
+    def forward(self, x):
+        """The emissions without a graph."""
+        with torch.no_grad():
+            return self.emissions_trainable(x.detach())
+
+    def loss(self, x, labels, cu_lens, chain=None, ignore_index=-100, reduction='mean'):
+        """esme.crf.CRF.loss of the emissions: a float32 device scalar with a grad_fn, no host synchronisation."""
+        return self.crf.loss(self.emissions_trainable(x), labels, cu_lens, chain=chain, ignore_index=ignore_index, reduction=reduction)
+
+    def predict(self, x, cu_lens, chain=None):
+        """(T,) int64: the Viterbi label of every residue, -100 on the rows outside chains."""
+        return self.crf.decode(self.forward(x), cu_lens, chain=chain)[0]
+
+    def marginals(self, x, cu_lens, chain=None):
+        return self.crf.marginals(self.forward(x), cu_lens, chain=chain)

@@ -135,7 +135,11 @@ class ResidueModel(nn.Module):
             return self.head(embed)
 
     def predict(self, token, pad_args=None, lora_names=None):
-        """The argmax label of every row."""
+        """The argmax label of every row; with a CRF head (esme.head.ResidueCRFHead) the Viterbi path, -100 outside the chains."""
+        if hasattr(self.head, 'crf'):
+            with torch.no_grad():
+                embed = self.plm.forward_representation(token, pad_args, lora_names=lora_names, layers=self.layers)
+                return self.head.predict(embed, pad_args[0])
         return self.forward(token, pad_args, lora_names=lora_names).argmax(dim=-1)
 
     def backbone_trains(self) -> bool:
@@ -156,6 +160,10 @@ class ResidueModel(nn.Module):
         """The cross entropy of the head's logits against `label` (aligned with `token`: ResidueLabeledDataset's `label`), differentiable
         in the head's parameters and in whatever the backbone trains."""
         embed = self.representation_trainable(token, pad_args, lora_names=lora_names, checkpoint_layers=checkpoint_layers)
+        if hasattr(self.head, 'crf'):                             # a CRF head scores label paths: it needs the sequences (`weight` does not apply)
+            if weight is not None:
+                raise ValueError('ResidueModel: class weights do not apply to a CRF head')
+            return self.head.loss(embed, label, pad_args[0], ignore_index=ignore_index, reduction=reduction)
         return self.head.loss(embed, label, ignore_index=ignore_index, weight=weight, reduction=reduction)
 
     def param_groups(self, lr=1e-5, lr_head=1e-4):

@@ -2,7 +2,7 @@
 Hugging Face's EsmForTokenClassification recipe.
 
   python tools/residue_finetune.py [CHECKPOINT.safetensors] [--steps 200] [--lora 8] [--lr 3e-3] [--lr-head 1e-2] [--layers 0]
-                                   [--token-per-batch 4000] [--sequences 256] [--checkpoint-layers] [--out FILE]
+                                   [--token-per-batch 4000] [--sequences 256] [--checkpoint-layers] [--crf] [--out FILE]
 
 Without a checkpoint a small synthetic ESM-2 (--synthetic-layers x --synthetic-dim) is used.  The task is synthetic and computable
 from the sequence, so the tool needs no data: the label of residue i is the class of the residue two positions on -- hydrophobic (0),
@@ -11,7 +11,9 @@ polar (1) or charged (2) -- and the last two residues of a protein carry no labe
 the adapters learn.  esme.data.ResidueLabeledDataset (token-budget batches, labels aligned with the packed tokens) ->
 esme.trainer.ResidueModel.loss_trainable: forward_trainable(logits=False, layers=...) -> ResidueHead.loss, the fused projection +
 cross-entropy kernel (include/esme_hip_linear_xent.h) -> esme.optim.AdamW.  Prints the loss per step and the final per-residue
-accuracy.  No step waits for the device except to print: the loss is a device scalar and is read after the optimiser step was queued."""
+accuracy.  --crf puts a linear-chain CRF on the head (esme.head.ResidueCRFHead, include/esme_hip_crf.h) and changes the task to one with a
+rule between neighbouring labels (make_segment_task): the loss is the CRF's negative log-likelihood, the prediction the Viterbi path.
+No step waits for the device except to print: the loss is a device scalar and is read after the optimiser step was queued."""
 import argparse
 import os
 import sys
@@ -37,6 +39,26 @@ def make_task(n_seq, seed=0, lo=20, hi=120):
         s = ''.join(RESIDUES[i] for i in torch.randint(0, len(RESIDUES), (n,), generator=g).tolist())
         seqs.append(s)
         labels.append([CLASS_OF[c] for c in s[SHIFT:]] + [-1] * SHIFT)
+    return seqs, labels
+
+
+def make_segment_task(n_seq, seed=0, lo=20, hi=120, run=4):
+    """(sequences, labels) with a rule between neighbouring labels that no single row shows: a charged residue opens a segment of
+    label 1 that lasts exactly `run` residues, everything else is label 0 -- so 0 -> 1 only at a charged residue and 1 -> 0 only after
+    `run` ones; label 2 marks the last residue of a segment (1 -> 2 -> 0).  The residues inside a segment are random."""
+    g = torch.Generator().manual_seed(seed)
+    seqs, labels = [], []
+    for _ in range(n_seq):
+        n = int(torch.randint(lo, hi + 1, (1,), generator=g))
+        s = ''.join(RESIDUES[i] for i in torch.randint(0, len(RESIDUES), (n,), generator=g).tolist())
+        lab, left = [], 0
+        for c in s:
+            if left == 0 and c in CHARGED:
+                left = run
+            lab.append(0 if left == 0 else (2 if left == 1 else 1))
+            left = max(left - 1, 0)
+        seqs.append(s)
+        labels.append(lab)
     return seqs, labels
 
 
@@ -96,6 +118,7 @@ def main():
     ap.add_argument('--synthetic-layers', type=int, default=2)
     ap.add_argument('--synthetic-dim', type=int, default=128)
     ap.add_argument('--checkpoint-layers', action='store_true')
+    ap.add_argument('--crf', action='store_true', help='a linear-chain CRF on the head, and the segment task')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--out', default='', help='append the printed lines to this file')
@@ -103,7 +126,7 @@ def main():
     import esme
     from esme import ESM, synthetic as syn
     from esme.data import ResidueLabeledDataset
-    from esme.head import ResidueHead
+    from esme.head import ResidueCRFHead, ResidueHead
     from esme.trainer import ResidueModel
     torch.manual_seed(args.seed)
     lines = []
@@ -123,16 +146,18 @@ def main():
     model.add_lora(rank=args.lora, alpha=args.lora, layers=('query', 'value', 'output'))
     model.mark_only_lora_as_trainable()
     layers = [int(i) for i in args.layers.split(',') if i.strip()]
-    head = ResidueHead(model.embed_dim * (1 + len(layers)), 3).to(args.device).requires_grad_(True)
+    head = (ResidueCRFHead if args.crf else ResidueHead)(model.embed_dim * (1 + len(layers)), 3).to(args.device).requires_grad_(True)
     net = ResidueModel(model, head, layers=layers)
     opt = esme.optim.AdamW(net.param_groups(args.lr, args.lr_head), weight_decay=args.weight_decay)
     n_head, n_plm = (sum(p.numel() for p in m.parameters() if p.requires_grad) for m in (head, model))
-    log(f'{type(model).__name__} ({len(model.layers)} layers, width {model.embed_dim}) + ResidueHead of width {net.width}: {n_head} head and '
-        f'{n_plm} adapter parameters train; label of residue i = class (hydrophobic / polar / charged) of residue i + {SHIFT}')
-    seqs, labels = make_task(args.sequences, args.seed)
+    task = make_segment_task if args.crf else make_task
+    what = 'segments of four residues opened by a charged residue' if args.crf else f'label of residue i = class (hydrophobic / polar / charged) of residue i + {SHIFT}'
+    log(f'{type(model).__name__} ({len(model.layers)} layers, width {model.embed_dim}) + {type(head).__name__} of width {net.width}: {n_head} head and '
+        f'{n_plm} adapter parameters train; {what}')
+    seqs, labels = task(args.sequences, args.seed)
     data = ResidueLabeledDataset(seqs, labels, args.token_per_batch, shuffle=True, random_state=args.seed)
     batches = [data[i] for i in range(len(data))]
-    held = ResidueLabeledDataset(*make_task(max(args.sequences // 4, 8), args.seed + 1), args.token_per_batch, shuffle=False)
+    held = ResidueLabeledDataset(*task(max(args.sequences // 4, 8), args.seed + 1), args.token_per_batch, shuffle=False)
     held = [held[i] for i in range(len(held))]
     log(f'accuracy before training: {accuracy(net, held, args.device):.4f} on held-out proteins (three classes)')
     train_steps(net, opt, batches, args.device, args.steps, args.checkpoint_layers, log)
