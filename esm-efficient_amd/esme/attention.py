@@ -23,14 +23,13 @@ unfused kernels (LN kernel, plain GEMM, rotary kernel) and are what the stage-ta
 """
 from __future__ import annotations
 
-import math
 import os
-from typing import NamedTuple, Optional
+from typing import Optional
 
 import torch
 from torch import nn
 
-from esme import _hip
+from esme import _hip, lora_fused
 from esme.nn import GELU, Derived, LayerNorm, Linear, pad_last, pad_rows, version_key
 from esme.rotary import RotaryEmbedding
 
@@ -189,13 +188,6 @@ class HalfPlan:
         return f"ext channels {0 if self.ext_sel is None else self.ext_sel.numel()}, q/k pairs {'on' if self.qk_pair else 'off'}{where}" + (', fixed-reference attention' if self.qp else '')
 
 
-class ExtBlock(NamedTuple):
-    """The extension columns [s B | 0] of a LoRA-extended weight on their own (`block`: (rows, X) bf16): what _lora_weights caches over a
-    quantised base, where the base columns are expanded from the codes per call (FlashMultiheadAttention._lora_extended).  (A tuple, so
-    that Derived.tensors() finds the block.)"""
-    block: torch.Tensor
-
-
 def has_pair_form(att) -> bool:
     """The block of attention module `att` has a q/k-pair form (HalfPlan.qk_pair): no q/k LayerNorm, head dim <= 64, width a multiple of 128."""
     return (not att.pre_layernorm) and att.head_pad in (16, 32, 64) and att.attn_dim % 128 == 0
@@ -341,7 +333,7 @@ class FlashMultiheadAttention(nn.Module):
         self.layer_index = 0        # position in the model's layer stack (set by the model; HalfPlan.pairs_at)
         self._q4_qkv = None         # esme.quantization.Q4Matrix pair when the layer is 4-bit
         self._q4_out = None
-        self._has_lora = False      # set by ESM2.add_lora: q / k / v / out may be esme.lora.LoRA wrappers
+        self._has_lora = False      # set by wrap_lora: q / k / v / out may be esme.lora.LoRA wrappers
         self._qlora = False         # set by ESM2.add_lora(quantized_base=True): adapters run and train over quantised q / k / v / out
 
     # -- weight layout ------------------------------------------------------
@@ -478,10 +470,7 @@ class FlashMultiheadAttention(nn.Module):
         E = self.attn_dim                                   # width of each of q, k, v (H * padded head dim)
         lw = None                                           # adapters: one esme_hip_lora_down in front of each GEMM that has some; that GEMM then runs over K = E + X
         if self._has_lora:
-            if self.training:
-                raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
-            if ctx is not None and (ctx.f16 or ctx.exact_attn):
-                raise NotImplementedError("LoRA adapters run in precision 'fast' only ('high', 'half' and 'exact' have no adapter path)")
+            lora_fused.check_mode(self.training, ctx is None or not (ctx.f16 or ctx.exact_attn))
             lw = self._lora_weights(lora_names, x_stats is not None)
         H, d = self.num_heads, self.head_pad
         rot_fusable = (self.rot_emb is not None and ctx is not None and not self.pre_layernorm
@@ -584,109 +573,43 @@ class FlashMultiheadAttention(nn.Module):
         a = ag.VarlenAttention.apply(q, k, v, cu_lens, int(max_len), self.num_heads, self.head_dim ** -0.5)
         return ag.lora_linear(a, self.out, lora_names)
 
-    # -- LoRA adapters (esme/lora.py): the delta rides in an extension K-tile of the projection's own GEMM --------------------
+    # -- LoRA adapters (esme/lora.py): the delta rides in an extension K-tile of the projection's own GEMM (esme/lora_fused.py) ------
+    def wrap_lora(self, names, wrap):
+        """ESM2.add_lora: `wrap(projection)` (an esme.lora.LoRA around it) takes the place of each of `names` (of 'q', 'k', 'v', 'out')."""
+        for p in names:
+            setattr(self, p, wrap(getattr(self, p)))
+        self._has_lora = True
+        self._derived.clear('lora')
+
     def _lora_weights(self, lora_names, fold: bool):
         """Derived weights of the adapters `lora_names` selects (None / empty: all), cached on the parameters' version counters and the
-        selection:  {'qkv': (X, A, c1A, bA, [W | s B | 0]) or None, 'out': (X, A, [W_o | s B | 0]) or None}.  The A matrices of all selected
-        adapters of q, k and v are stacked to one (R, E) operand of esme_hip_lora_down; s B of each sits in the rows of its own
-        projection, zero elsewhere.  `fold`: for the LayerNorm-folded QKV GEMM, whose epilogue multiplies the accumulator by rstd -- A
-        carries gamma (A' = bf16(gamma * A)), c1A = rowsum(A'), bA = A beta, and the kernel writes LN(x) A^T / rstd.
-        On a quantised base that opted in (add_lora(quantized_base=True)) no bf16 copy of W is built: the last element of either tuple is
-        an ExtBlock, the (rows, X) extension columns [s B | 0] alone, keyed as above minus the base weight; _lora_extended puts it next to
-        the base in the weight scratch per call."""
-        from esme.lora import LoRA, ext_width
-        if self.padded:
-            raise NotImplementedError('LoRA adapters are not implemented for padded layouts (head dim 24 / a width that is not a multiple of 64)')
+        selection:  {'qkv': (X, A, c1A, bA, [W | s B | 0]) or None, 'out': (X, A, [W_o | s B | 0]) or None}  (lora_fused.build; q, k, v are
+        consecutive E-row blocks).  `fold`: for the LayerNorm-folded QKV GEMM.  Quantised base (opted in): the last elements are ExtBlocks."""
         quantised = self._q4_qkv is not None or self._q4_out is not None
-        if quantised and not self._qlora:
-            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters, '
-                                      'unless they were attached with add_lora(quantized_base=True))')
-        mods = {p: getattr(self, p) for p in ('q', 'k', 'v', 'out') if isinstance(getattr(self, p), LoRA)}
-        sel = {p: m.select(lora_names) for p, m in mods.items()}
-        params = [t for p, m in mods.items() for t in m.params(sel[p])]
-        E = self.embed_dim
-        if quantised:
-            # the key of the unquantised form minus the base weight; the folded A' carries the LayerNorm, so its version stays
-            key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), 'quantised base',
-                   version_key(*params, *((self.norm.weight, self.norm.bias) if fold else ())))
-            base = None
-        else:
+        lora_fused.check_base(self.padded, quantised, self._qlora)
+        names = ('q', 'k', 'v', 'out')
+        base = base_key = None
+        if not quantised:
             base = (self._pack_fold() if fold else self._pack())[0]
-            key = (bool(fold), tuple(sorted(sel.items())), tuple(float(m.scaling) for m in mods.values()), self._derived.key('fold' if fold else 'pack'),
-                   version_key(self.out.weight, *params))
-
-        def extended(w, rows, X):
-            """(the weight form, its extension columns as a view): (rows, E + X) zeros with the base `w` in the first E columns; on a
-            quantised base (`w` None) an ExtBlock, the (rows, X) columns alone."""
-            if w is None:
-                we = ExtBlock(torch.zeros(rows, X, dtype=torch.bfloat16, device=self.norm.weight.device))
-                return we, we.block
-            we = torch.zeros(rows, E + X, dtype=torch.bfloat16, device=w.device)
-            we[:, :E] = w
-            return we, we[:, E:]
-
-        def build():
-            res = {'qkv': None, 'out': None}
-            blocks = [(i, *mods[p].stacked(sel[p])) for i, p in enumerate(('q', 'k', 'v')) if p in mods]
-            if blocks:
-                A = torch.cat([b[1] for b in blocks], dim=0).contiguous()
-                X = ext_width(A.shape[0])
-                c1A = bA = None
-                if fold:
-                    Af = A.float()
-                    A = (Af * self.norm.weight.data.float().unsqueeze(0)).to(torch.bfloat16).contiguous()
-                    c1A = A.float().sum(dim=1).contiguous()
-                    bA = (Af @ self.norm.bias.data.float()).contiguous() if self.norm.bias is not None else torch.zeros_like(c1A)
-                we, ext = extended(base, 3 * E, X)
-                o = 0
-                for i, a, b in blocks:
-                    ext[i * E:(i + 1) * E, o:o + a.shape[0]] = b.to(torch.bfloat16)
-                    o += a.shape[0]
-                res['qkv'] = (X, A, c1A, bA, we)
-            if 'out' in mods:
-                A, B = mods['out'].stacked(sel['out'])
-                X = ext_width(A.shape[0])
-                we, ext = extended(None if quantised else self.out.weight.data, E, X)
-                ext[:, :B.shape[1]] = B.to(torch.bfloat16)
-                res['out'] = (X, A.contiguous(), we)
-            return res
-        return self._derived.get('lora', key, build)
-
-    def _lora_extended(self, which: str, entry, fold: bool = False):
-        """[W | s B | 0] of the _lora_weights entry of the GEMM `which` ('qkv' / 'out'): the cached tensor, or, on a quantised base, the base
-        expanded into a (rows, K + X) view of the shared weight scratch (esme.quantization.Q4Matrix) with the cached extension block copied
-        into the columns K .. K + X - 1 -- per call, like every use of a quantised weight; the GEMM that reads it is next on the stream."""
-        we = entry[-1]
-        if not isinstance(we, ExtBlock):
-            return we
-        q4 = self._q4_qkv if which == 'qkv' else self._q4_out
-        w = (q4.folded(entry[0]) if fold else q4.plain(entry[0]))[0]
-        w[:, q4.cols:].copy_(we.block)
-        return w
+            base_key = self._derived.key('fold' if fold else 'pack')
+        return lora_fused.entries(self._derived, ('qkv', 'out'), [getattr(self, p) for p in names], lora_names, fold, self.norm, base, base_key, torch.vstack, names)
 
     def lora_ext_widths(self, lora_names):
         """(X of the QKV GEMM, X of the out-projection) for this selection (0: that GEMM has no adapter)."""
-        lw = self._lora_weights(lora_names, True)
-        return (lw['qkv'][0] if lw['qkv'] else 0, lw['out'][0] if lw['out'] else 0)
+        return lora_fused.ext_widths(self._lora_weights(lora_names, True))
 
     def _qkv_lora_unfused(self, x, lw, rot):
-        """LayerNorm kernel -> [h | h A^T] -> plain QKV GEMM over [W | s B] (the stage form, and the path without LayerNorm fold);
-        without adapters (`lw` None or no q / k / v adapter selected) LayerNorm kernel -> plain QKV GEMM."""
+        """LayerNorm kernel (-> [h | h A^T] with adapters `lw`) -> plain QKV GEMM (over [W | s B]): the stage form, and the path without LayerNorm fold."""
         if lw is None or lw['qkv'] is None:
             w, b, _, _ = self._weights_qkv(False)
             return _hip.gemm_fused(self.norm(x), w, b, rot=rot)
-        X, A = lw['qkv'][:2]
-        E = self.embed_dim
-        he = torch.empty(x.shape[0], E + X, dtype=torch.bfloat16, device=x.device)
-        self.norm(x, out=he[:, :E])
-        _hip.lora_down(he[:, :E], A, he[:, E:])
+        he = lora_fused.ln_operand(x, lw['qkv'], self.norm)
         b = self._q4_qkv.bias if self._q4_qkv is not None else self._pack()[1]
-        return _hip.gemm_fused(he, self._lora_extended('qkv', lw['qkv']), b, rot=rot)
+        return _hip.gemm_fused(he, lora_fused.expand(self._q4_qkv, lw['qkv']), b, rot=rot)
 
     def _qkv_operands(self, x, x_stats, ctx, lw, f16, pair_ext):
-        """(operand, W', c1, c2) of the LayerNorm-folded QKV GEMM.  With q / k / v adapters (`lw`: _lora_weights): the operand is [x | u] with
-        u = the adapters' down-projection, written here by esme_hip_lora_down, and W' = [W' | s B | 0].  With every lora_B zero the extension
-        adds exact zeros to the fp32 accumulators, so the result equals the block's without adapters bit for bit."""
+        """(operand, W', c1, c2) of the LayerNorm-folded QKV GEMM.  With q / k / v adapters (`lw`: _lora_weights): [x | u] (lora_fused.folded_operand)
+        and W' = [W' | s B | 0].  With every lora_B zero the extension adds exact zeros to the fp32 accumulators: bit-equal to no adapters."""
         if lw is None or lw['qkv'] is None:
             wf, _, c1, c2 = self._weights_qkv(True, f16, pair_ext)
             return x, wf, c1, c2
@@ -694,27 +617,24 @@ class FlashMultiheadAttention(nn.Module):
             c1, c2 = self._q4_qkv.c1, self._q4_qkv.c2
         else:
             _, _, c1, c2 = self._weights_qkv(True, f16, pair_ext)
-        X, A, c1A, bA = lw['qkv'][:4]
-        E = self.embed_dim
-        xe = ctx.lora_x if ctx is not None else None
-        if xe is None or xe.data_ptr() != x.data_ptr() or xe.stride(0) != x.stride(0) or xe.shape[1] < E + X:
-            xe = torch.empty(x.shape[0], E + X, dtype=torch.bfloat16, device=x.device)       # (a caller outside the model's forward: x moves once)
-            xe[:, :E].copy_(x)
-        _hip.lora_down(xe[:, :E], A, xe[:, E:E + X], ln=(x_stats, self.embed_dim, self.norm.eps, c1A, bA))
-        return xe[:, :E + X], self._lora_extended('qkv', lw['qkv'], True), c1, c2
+        return lora_fused.folded_operand(x, lw['qkv'], x_stats, self.norm, ctx), lora_fused.expand(self._q4_qkv, lw['qkv'], True), c1, c2
 
     def _out_operands(self, lw, f16, q, k, v, *attn_args, **attn_kw):
-        """Runs the attention kernel (_attn) and returns (its output, W_o, b_o), the operands of the out-projection.  With an out adapter
-        (`lw`: _lora_weights) the output lands in the first E columns of a (T, E + X) buffer, esme_hip_lora_down fills the rest, and
-        W_o = [W_o | s B | 0]."""
+        """Runs the attention kernel (_attn) and returns (its output, W_o, b_o), the operands of the out-projection.  With an out adapter (`lw`:
+        _lora_weights) the output lands in the first E columns of a (T, E + X) buffer, esme_hip_lora_down fills the rest, W_o = [W_o | s B | 0]."""
         if lw is None or lw['out'] is None:
             return (self._attn(q, k, v, *attn_args, **attn_kw), *self._weights_out(f16))
-        X, A = lw['out'][:2]
         E = self.embed_dim
-        a = torch.empty(q.shape[0], E + X, dtype=torch.bfloat16, device=q.device)
-        self._attn(q, k, v, *attn_args, out=a[:, :E], **attn_kw)
-        _hip.lora_down(a[:, :E], A, a[:, E:])
-        return a, self._lora_extended('out', lw['out']), self.out.bias
+        a, head = lora_fused.tail_buffer(q.shape[0], E, lw['out'], q.device)
+        self._attn(q, k, v, *attn_args, out=head, **attn_kw)
+        return lora_fused.fill_tail(a, head, lw['out']), lora_fused.expand(self._q4_out, lw['out']), self.out.bias
+
+
+def _interleave32(mats):
+    """The rows of one matrix as they are, of two (SwiGLU's gate, fc) in alternating blocks of 32: the row order of the FFN up weight."""
+    F, E = mats[0].shape
+    assert F % 32 == 0
+    return torch.cat([m.view(F // 32, 1, 32, E) for m in mats], dim=1).reshape(len(mats) * F, E)
 
 
 class SwiGLU(nn.Module):
@@ -735,11 +655,7 @@ class SwiGLU(nn.Module):
         return self._derived.get('pack', version_key(self.activation.weight, self.fc.weight), self._build_pack)
 
     def _build_pack(self):
-        F, E = self.activation.weight.shape
-        assert F % 32 == 0
-        g = self.activation.weight.data.view(F // 32, 1, 32, E)
-        f = self.fc.weight.data.view(F // 32, 1, 32, E)
-        return torch.cat((g, f), dim=1).reshape(2 * F, E).contiguous()
+        return _interleave32((self.activation.weight.data, self.fc.weight.data)).contiguous()
 
     def forward(self, x, out=None, ln=None, packed=None):
         w = self._pack()
@@ -871,98 +787,34 @@ class FlashTransformerLayer(nn.Module):
         self._derived.clear('lora')
 
     def _ffn_lora_weights(self, lora_names, fold: bool):
-        """Derived weights of the FFN adapters `lora_names` selects (None / empty: all), cached like FlashMultiheadAttention._lora_weights on
-        the selection, the scalings, the parameters' version counters and the base form's key:
-        {'up': (X, A, c1A, bA, [W | s B | 0]) or None, 'down': (X, A, [W_d | s B | 0]) or None}.  SwiGLU: the gate's adapter rows come
-        first in A, then fc's, and the rows of s B follow the 32-row gate / fc interleave of SwiGLU._build_pack -- the gate adapter's
-        columns are zero in the fc rows and the other way round.  `fold`: for the LayerNorm-folded up-projection (A' = bf16(gamma A),
-        c1A, bA from `final[0]`).  On a quantised base that opted in the last element of either tuple is an ExtBlock (_ffn_lora_extended)."""
-        from esme.lora import LoRA
-        if self.padded:
-            raise NotImplementedError('LoRA adapters are not implemented for padded layouts (head dim 24 / a width that is not a multiple of 64)')
+        """Derived weights of the FFN adapters `lora_names` selects (None / empty: all), cached like FlashMultiheadAttention._lora_weights:
+        {'up': (X, A, c1A, bA, [W | s B | 0]) or None, 'down': (X, A, [W_d | s B | 0]) or None}  (lora_fused.build).  SwiGLU: the gate's
+        adapter rows come first in A, then fc's, and the rows of s B follow the 32-row gate / fc interleave of SwiGLU._build_pack -- the
+        gate adapter's columns are zero in the fc rows and the other way round.  `fold`: for the LayerNorm-folded up-projection (`final[0]`)."""
         quantised = self._q4_up is not None or self._q4_down is not None
-        if quantised and not self._qlora:
-            raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters, '
-                                      'unless they were attached with add_lora(quantized_base=True))')
+        lora_fused.check_base(self.padded, quantised, self._qlora)
         ups, (_, down) = self._ffn_projections()
-        mods = [m for _, m in (*ups, ('', down)) if isinstance(m, LoRA)]
-        sel = tuple(m.select(lora_names) for m in mods)
-        params = [t for m, s in zip(mods, sel) for t in m.params(s)]
-        scalings = tuple(float(m.scaling) for m in mods)
-        ln = self.final[0]
-        if quantised:
-            key = (bool(fold), sel, scalings, 'quantised base', version_key(*params, *((ln.weight, ln.bias) if fold else ())))
-        else:
-            if fold:
-                self._pack_fold()
+        base = base_key = None
+        if not quantised:
+            base = (self._pack_fold() if fold else self._weights_up(False))[0].data
             base_key = self._derived.key('fold') if fold else version_key(*(m.weight for _, m in ups))
-            key = (bool(fold), sel, scalings, base_key, version_key(down.weight, *params))
-        return self._derived.get('lora', key, self._build_ffn_lora, lora_names, fold, quantised)
-
-    def _build_ffn_lora(self, lora_names, fold: bool, quantised: bool):
-        from esme.lora import LoRA, ext_width
-        ups, (_, down) = self._ffn_projections()
-        ln, E, F = self.final[0], self.embed_dim, ups[0][1].out_features
-        dev = ln.weight.device
-        res = {'up': None, 'down': None}
-        blocks = [(i, *m.stacked(m.select(lora_names))) for i, (_, m) in enumerate(ups) if isinstance(m, LoRA)]
-        if blocks:
-            A = torch.cat([b[1] for b in blocks], dim=0).contiguous()
-            X = ext_width(A.shape[0])
-            c1A = bA = None
-            if fold:
-                Af = A.float()
-                A = (Af * ln.weight.data.float().unsqueeze(0)).to(torch.bfloat16).contiguous()
-                c1A = A.float().sum(dim=1).contiguous()
-                bA = (Af @ ln.bias.data.float()).contiguous() if ln.bias is not None else torch.zeros_like(c1A)
-            parts = [torch.zeros(F, X, dtype=torch.bfloat16, device=dev) for _ in ups]     # the extension columns per projection ...
-            o = 0
-            for i, a, b in blocks:
-                parts[i][:, o:o + a.shape[0]] = b.to(torch.bfloat16)
-                o += a.shape[0]
-            ext = parts[0] if len(parts) == 1 else torch.cat([p.view(F // 32, 1, 32, X) for p in parts], dim=1).reshape(2 * F, X)      # ... interleaved like the weight
-            if quantised:
-                we = ExtBlock(ext.contiguous())
-            else:
-                we = torch.cat(((self._pack_fold() if fold else self._weights_up(False))[0].data, ext), dim=1).contiguous()
-            res['up'] = (X, A, c1A, bA, we)
-        if isinstance(down, LoRA):
-            A, B = down.stacked(down.select(lora_names))
-            X = ext_width(A.shape[0])
-            ext = torch.zeros(E, X, dtype=torch.bfloat16, device=dev)
-            ext[:, :B.shape[1]] = B.to(torch.bfloat16)
-            res['down'] = (X, A.contiguous(), ExtBlock(ext) if quantised else torch.cat((down.weight.data, ext), dim=1).contiguous())
-        return res
-
-    def _ffn_lora_extended(self, which: str, entry, fold: bool = False):
-        """[W | s B | 0] of the _ffn_lora_weights entry `which` ('up' / 'down'): the cached tensor, or, on a quantised base, the per-call
-        expansion in the weight scratch with the cached extension block copied next to it (FlashMultiheadAttention._lora_extended)."""
-        we = entry[-1]
-        if not isinstance(we, ExtBlock):
-            return we
-        q4 = self._q4_up if which == 'up' else self._q4_down
-        w = (q4.folded(entry[0]) if fold else q4.plain(entry[0]))[0]
-        w[:, q4.cols:].copy_(we.block)
-        return w
+        return lora_fused.entries(self._derived, ('up', 'down'), [*(m for _, m in ups), down], lora_names, fold, self.final[0], base, base_key, _interleave32)
 
     def ffn_lora_ext_widths(self, lora_names):
         """(X of the FFN up-projection, X of the down-projection) for this selection (0: that GEMM has no adapter)."""
         if not self._has_lora:
             return 0, 0
-        lw = self._ffn_lora_weights(lora_names, True)
-        return (lw['up'][0] if lw['up'] else 0, lw['down'][0] if lw['down'] else 0)
+        return lora_fused.ext_widths(self._ffn_lora_weights(lora_names, True))
 
     def _ffn_lora(self, x, alpha, stream, x_stats, stats_out, lw, epi, ctx):
-        """_ffn with adapters (`lw`: _ffn_lora_weights, precision 'fast').  Up: the operand is [x | u] (LayerNorm-folded: the stream buffer
-        ctx.lora_x with u from esme_hip_lora_down_ln on the FFN LayerNorm's statistics; else [LN(x) | u] in a buffer of its own) against
-        [W | s B | 0].  Down: the up GEMM writes its activation into the first F columns of a (T, F + X) buffer, esme_hip_lora_down
+        """_ffn with adapters (`lw`: _ffn_lora_weights, precision 'fast').  Up: [x | u] (lora_fused.folded_operand, or unfolded .ln_operand)
+        against [W | s B | 0].  Down: the up GEMM writes its activation into the first F columns of a (T, F + X) buffer, esme_hip_lora_down
         (K = F) fills the rest, and the residual GEMM runs over K = F + X.  Every lora_B zero: the extensions add exact zeros."""
         up, down = lw['up'], lw['down']
         ups, (_, dmod) = self._ffn_projections()
-        T, E, F = x.shape[0], self.embed_dim, ups[0][1].out_features
+        F = ups[0][1].out_features
         ln = self.final[0]
-        mid = torch.empty(T, F + down[0], dtype=torch.bfloat16, device=x.device) if down is not None else None
-        act = mid[:, :F] if mid is not None else None
+        mid, act = lora_fused.tail_buffer(x.shape[0], F, down, x.device) if down is not None else (None, None)
         if x_stats is not None:
             if up is None or self._q4_up is None:
                 w, _, c1, c2 = self._weights_up(True)
@@ -970,31 +822,20 @@ class FlashTransformerLayer(nn.Module):
                 c1, c2 = self._q4_up.c1, self._q4_up.c2
             a_op = x
             if up is not None:
-                X, A, c1A, bA = up[:4]
-                xe = ctx.lora_x if ctx is not None else None
-                if xe is None or xe.data_ptr() != x.data_ptr() or xe.stride(0) != x.stride(0) or xe.shape[1] < E + X:
-                    xe = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)       # (a caller outside the model's forward: x moves once)
-                    xe[:, :E].copy_(x)
-                _hip.lora_down(xe[:, :E], A, xe[:, E:E + X], ln=(x_stats, E, ln.eps, c1A, bA))
-                a_op, w = xe[:, :E + X], self._ffn_lora_extended('up', up, True)
-            act = _hip.gemm_fused(a_op, w, None, epi, out=act, ln=(x_stats, E, ln.eps, c1, c2, None))
+                a_op, w = lora_fused.folded_operand(x, up, x_stats, ln, ctx), lora_fused.expand(self._q4_up, up, True)
+            act = _hip.gemm_fused(a_op, w, None, epi, out=act, ln=(x_stats, self.embed_dim, ln.eps, c1, c2, None))
         else:
             if up is None:
                 w, b, _, _ = self._weights_up(False)
                 a_op = ln(x)
             else:
-                X, A = up[:2]
-                a_op = torch.empty(T, E + X, dtype=torch.bfloat16, device=x.device)
-                ln(x, out=a_op[:, :E])
-                _hip.lora_down(a_op[:, :E], A, a_op[:, E:])
-                w = self._ffn_lora_extended('up', up)
+                a_op, w = lora_fused.ln_operand(x, up, ln), lora_fused.expand(self._q4_up, up)
                 b = self._q4_up.bias if self._q4_up is not None else (ups[0][1].bias if len(ups) == 1 else None)
             act = _hip.gemm_fused(a_op, w, b, epi, out=act)
         if down is None:
             wd, bd = self._weights_down()
         else:
-            _hip.lora_down(act, down[1], mid[:, F:])
-            act, wd = mid, self._ffn_lora_extended('down', down)
+            act, wd = lora_fused.fill_tail(mid, act, down), lora_fused.expand(self._q4_down, down)
             bd = self._q4_down.bias if self._q4_down is not None else dmod.bias
         return _hip.gemm_fused(act, wd, bd, _hip.EPI_RESIDUAL, alpha=alpha, stats_out=stats_out, **stream)
 
@@ -1004,10 +845,7 @@ class FlashTransformerLayer(nn.Module):
         epi = _hip.EPI_GELU if self.final_activation == 'gelu' else _hip.EPI_SWIGLU
         f16 = x.dtype == torch.float16                       # precision 'half': the operand type travels with the tensors
         if self._has_lora:
-            if self.training:
-                raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
-            if f16 or 'resid' not in stream:
-                raise NotImplementedError("LoRA adapters run in precision 'fast' only ('high', 'half' and 'exact' have no adapter path)")
+            lora_fused.check_mode(self.training, not f16 and 'resid' in stream)
             lw = self._ffn_lora_weights(lora_names, x_stats is not None)
             if lw['up'] is not None or lw['down'] is not None:
                 return self._ffn_lora(x, alpha, stream, x_stats, stats_out, lw, epi, ctx)

@@ -29,7 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
-from esme import _hip, halfmode
+from esme import _hip, halfmode, lora_fused
 from esme.alphabet import Alphabet, Alphabet3
 from esme.attention import FlashTransformerLayer, ForwardContext, padded_head_dim
 from esme.head import RobertaLMHead
@@ -199,8 +199,8 @@ class ESM2(nn.Module):
         OWN data, packed like a forward's input -- calibrated on in addition to the built-in whole-vocabulary batch (the plan is then decided
         on what the model will really see; the run-time guard covers the rest)."""
         assert mode in ('fast', 'high', 'half', 'exact'), mode
-        if mode != 'fast' and self.has_lora:
-            raise NotImplementedError(f"precision {mode!r} has no LoRA adapter path: adapters run in precision 'fast' only")
+        if self.has_lora:
+            lora_fused.check_precision(mode)
         changed = mode != self.precision
         self.precision = mode
         if halfmode.configure(self, robust, calib) or changed:
@@ -635,10 +635,8 @@ class ESM2(nn.Module):
         be applied (any precision but 'fast', train mode): a forward never runs silently without them."""
         if not self.has_lora:
             return None
-        if self.precision != 'fast':
-            raise NotImplementedError(f"precision {self.precision!r} has no LoRA adapter path: adapters run in precision 'fast' only")
-        if self.training:
-            raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
+        lora_fused.check_precision(self.precision)
+        lora_fused.check_mode(self.training)
         have = self.lora_names()
         if not lora_names:
             return tuple(have)
@@ -686,8 +684,7 @@ class ESM2(nn.Module):
             'layers must be a subset of {"query", "value", "key", "output", "ffn_up", "ffn_down"}'
         if self.has_lora:
             raise NotImplementedError('LoRA adapters are already attached to this model (a second set would wrap the first)')
-        if self.precision != 'fast':
-            raise NotImplementedError(f"precision {self.precision!r} has no LoRA adapter path: adapters run in precision 'fast' only")
+        lora_fused.check_precision(self.precision)
         quantised = getattr(self, 'quantization', None) is not None
         if quantised and not quantized_base:
             raise NotImplementedError('LoRA adapters need unquantised bfloat16 base weights (quantization= is not supported with adapters; '
@@ -699,14 +696,14 @@ class ESM2(nn.Module):
         self.lora_kwargs = {'rank': rank, 'alpha': alpha, 'dropout_p': dropout_p,
                             'layers': [long for long in (*(l for l, _ in self._LORA_TARGETS), *self._LORA_FFN_TARGETS) if long in wanted],
                             'names': adapter_names}
+
+        def wrap(lin):
+            return LoRA(lin, rank=rank, alpha=alpha, dropout_p=dropout_p, names=adapter_names)
+
         for layer in self.layers:
             att = layer.self_attn
-            for long, short in self._LORA_TARGETS:
-                if long in wanted:
-                    setattr(att, short, LoRA(getattr(att, short), rank=rank, alpha=alpha, dropout_p=dropout_p, names=adapter_names))
-            layer.wrap_ffn_lora('ffn_up' in wanted, 'ffn_down' in wanted,
-                                lambda lin: LoRA(lin, rank=rank, alpha=alpha, dropout_p=dropout_p, names=adapter_names))
-            att._has_lora = True
+            att.wrap_lora([short for long, short in self._LORA_TARGETS if long in wanted], wrap)
+            layer.wrap_ffn_lora('ffn_up' in wanted, 'ffn_down' in wanted, wrap)
             att._qlora = layer._qlora = bool(quantised)      # (quantised here means: and opted in)
         self.__dict__['_lora_attached'] = True
         self._qlora = bool(quantised)

@@ -9,7 +9,7 @@ the adapters could no longer be selected per call).  The delta rides in an EXTEN
     [x | u] [W | s B]^T = x W^T + u (s B)^T,        u = x A^T   (esme_hip_lora_down, written next to x in the same buffer)
 
 so it accumulates in fp32 inside the MFMA chain and every fused epilogue of the hot path (LayerNorm fold, rotary, q pre-scale,
-residual, row statistics, GELU, SwiGLU) is untouched (esme/attention.py).  The wrapped projections are the
+residual, row statistics, GELU, SwiGLU) is untouched (esme/lora_fused.py, esme/attention.py).  The wrapped projections are the
 reference's four (q, k, v, out of the attention block) and, beyond it, the FFN's (`ESM2.add_lora(layers=(..., 'ffn_up', 'ffn_down'))`:
 the up-projection -- SwiGLU: its gate and fc, one wrapper each -- and the down-projection, whose adapter reads K = the FFN width).
 That fused forward is for inference: it has no
@@ -29,6 +29,7 @@ from esme.nn import Derived, version_key
 
 EXT_TILE = 64            # the GEMM's K tile: extension widths are multiples of it
 MAX_EXT = 256            # widest extension esme_hip_lora_down is built for
+INFERENCE_ONLY = 'LoRA adapters run for inference only: call model.eval() (no backward, no dropout)'     # (raised here and by esme.lora_fused.check_mode)
 
 
 def ext_width(rows: int) -> int:
@@ -122,7 +123,7 @@ class LoRA(nn.Module):
         """layer(x) + sum_n scaling * B_n A_n x as ONE GEMM over [x | x A^T] (the stage form; the model's hot path fuses the
         adapters of q, k and v into its packed QKV GEMM: esme.attention.FlashMultiheadAttention)."""
         if self.training:
-            raise NotImplementedError('LoRA adapters run for inference only: call model.eval() (no backward, no dropout)')
+            raise NotImplementedError(INFERENCE_ONLY)
         (we, A), b = self.stage_form(names), self.layer.bias
         shape = x.shape
         x2 = x.reshape(-1, shape[-1])

@@ -106,7 +106,7 @@ class Q4Matrix:
 
     def _expand_ext(self, col_scale, ext: int):
         """The expansion into the first `cols` columns of a (rows, cols + ext) scratch view; returns the whole view.  The `ext` columns
-        (the extension K-tile of LoRA adapters over a quantised base: esme.attention._lora_weights) are the caller's to fill."""
+        (the extension K-tile of LoRA adapters over a quantised base: esme.lora_fused.ExtBlock) are the caller's to fill."""
         view = self.scratch.view(self.rows, self.cols + ext, self.codes.device)
         self._expand(col_scale, view[:, :self.cols] if ext else view)
         return view
